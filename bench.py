@@ -10,7 +10,15 @@ For N>1 (torchrun, one process per GPU) each rank trains on its own 16 images
 and gradients are all-reduced over RCCL, bucketed and overlapped with the
 backward (weak scaling).
 
-Prints ONE JSON line (rank 0).  Extra objects:
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints ONE JSON line (rank 0) with the headline figure (`value`,
+`ms_per_step`); everything else below is measured only with `--full` and is null
+in a plain run's line.  `--dump-outputs DIR` writes what the last timed step
+handed back (its loss, the parameters it updated, the gradients it left in
+`.grad`) as DIR/<name>.npy (float32); the inputs are seeded, so two builds run
+with the same arguments can be compared array for array.
+
+Extra objects of a `--full` run:
   roofline      dominant kernel instantiation, achieved algorithmic TFLOP/s or
                 GB/s measured with HIP events on the compute stream over the timed
                 region, against the MI355X peak (MI355X_MICROARCH.md)
@@ -543,8 +551,36 @@ class Trainer:
         return round(1e3 * sorted(ts)[n // 2], 3)
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all arrays together
+
+
+def snapshot_outputs(tr, loss):
+    """What a caller of the timed step receives from its last call, as host float32
+    arrays: the loss it returns, the parameters it updated and the clipped gradients
+    it left in `.grad` (each flattened and concatenated in model.parameters() order)."""
+    ps = list(tr.model.parameters())
+    out = {"loss": loss.detach().float().reshape(-1).cpu().numpy(),
+           "params": torch.cat([p.detach().float().reshape(-1) for p in ps]).cpu().numpy()}
+    if all(p.grad is not None for p in ps):
+        out["grads"] = torch.cat([p.grad.detach().float().reshape(-1) for p in ps]).cpu().numpy()
+    return out
+
+
+def write_outputs(dirname, arrays):
+    """DIR/<name>.npy, float32; an array past its share of DUMP_LIMIT_BYTES is cut to a
+    fixed (seeded) sorted sample of its elements."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) // 4
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 DENSE_LEVELS = (0, 1)
-PROFILE_PASSES = 3   # serialised profiling passes behind each dense_conv_path figure (median reported)
+PROFILE_PASSES = 3  # serialised profiling passes behind each dense_conv_path figure (median reported)
 
 
 def dense_conv_path_median(profs, batch):
@@ -702,6 +738,12 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--base-filters", type=int, default=32)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-kernel profile and roofline (PMC "
+                         "traffic passes), the eager pass and host issue times, the batch-32 and fp32 lines, the CPU "
+                         "baseline and the sampler / forward legs (the --no-* options below trim a --full run)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (loss, updated parameters, gradients) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--layer-report", default="", help="write a per-kernel time table (json) here")
@@ -720,6 +762,10 @@ def main():
     ap.add_argument("--deadline-s", type=float, default=0.0,
                     help="wall-clock limit per rank and per launch (0: derived from --steps / --warmup)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.layer_report and not args.full:
+        ap.error("--layer-report needs the profiling passes of --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch(args, sys.argv[1:]))
@@ -808,10 +854,13 @@ def main():
 
     # per-kernel profile pass (not timed): find the dominant kernel instantiation
     # (backward serialised: every launch timed alone, not beside the other stream)
-    profs = [tr.profile() for _ in range(PROFILE_PASSES)]
-    prof = profs[0]
-    table = prof.summary()
-    dom = max(table, key=lambda k: table[k]["ms"])
+    full = args.full
+    profs = table = dom = None
+    if full:
+        profs = [tr.profile() for _ in range(PROFILE_PASSES)]
+        prof = profs[0]
+        table = prof.summary()
+        dom = max(table, key=lambda k: table[k]["ms"])
     if rank == 0 and args.layer_report:
         with open(args.layer_report, "w") as f:
             json.dump({k: {kk: (sorted(vv) if isinstance(vv, set) else vv) for kk, vv in d.items()}
@@ -822,18 +871,30 @@ def main():
     # timed region.  Eager: events around the dominant kernel's launches inside it.
     # Graph: the replays are timed; the dominant kernel's launch times come from an
     # eager pass of the same steps right after (events cannot be timed inside a replay)
-    live = EventTracer(keys={dom})
+    # Without --full only the steps themselves run: no kernel events, no eager pass
+    # after the replays (an eager run still times its own all-reduces for N > 1).
+    live = EventTracer(keys={dom}) if full else None
     sync = getattr(tr.unet._rdn_flat, "grad_sync", None) if world > 1 else None
+    dumped = None
     if graph:
         el, loss = tr.timed(args.steps, world, None)
-        if sync is not None:
-            sync.timing = []   # (events only in the eager pass: a replay cannot be timed inside)
-        el_eager, _ = tr.timed(args.steps, world, live)
+        if rank == 0 and args.dump_outputs:
+            dumped = snapshot_outputs(tr, loss)
+        el_eager = None
+        if full:
+            if sync is not None:
+                sync.timing = []   # (events only in the eager pass: a replay cannot be timed inside)
+            el_eager, _ = tr.timed(args.steps, world, live)
     else:
         if sync is not None:
             sync.timing = []
         el, loss = tr.timed(args.steps, world, live)
+        if rank == 0 and args.dump_outputs:
+            dumped = snapshot_outputs(tr, loss)
         el_eager = el
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
+        del dumped
     exposed = exposed_graph = None
 
     def over_ranks(mine, note):
@@ -844,13 +905,13 @@ def main():
         vals = [v for v in per if v is not None]
         return {"per_rank": per, "max": max(vals) if vals else None,
                 "mean": round(sum(vals) / len(vals), 4) if vals else None, "unit": "ms per step", "note": note}
-    if sync is not None:
+    if sync is not None and sync.timing is not None:
         mine = sync.exposed_ms()
         sync.timing = None
         exposed = over_ranks(mine, "eager pass of the timed steps: end of the last gradient bucket's all-reduce "
                                    "on the comm stream minus the end of the backward on the compute stream "
                                    "(0 when hidden)")
-        if graph and sync.stamps is not None:
+        if full and graph and sync.stamps is not None:
             # the replayed step itself: its GradSync stamp kernels, read after each of
             # `steps` further (untimed) replays
             from vub_image_denoising_amd import _hip as H
@@ -866,18 +927,21 @@ def main():
                                        "stream before and after its wait on the last all-reduce, less the launch "
                                        "gap of two back-to-back stamps (ddp.exposure_from_stamps)")
     if world > 1:
-        tt = torch.tensor([el, el_eager], device=dev)
+        tt = torch.tensor([el, el if el_eager is None else el_eager], device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        el, el_eager = tt.tolist()
+        el, tt_eager = tt.tolist()
+        el_eager = None if el_eager is None else tt_eager
     loss_v = loss.item()
-    d = live.summary()[dom]
-    host_ms = tr.host_issue_ms() if world == 1 else None
-    tr.eager = True
-    host_eager_ms = tr.host_issue_ms() if (world == 1 and graph) else host_ms
-    tr.eager = False
+    d = host_ms = host_eager_ms = None
+    if full:
+        d = live.summary()[dom]
+        host_ms = tr.host_issue_ms() if world == 1 else None
+        tr.eager = True
+        host_eager_ms = tr.host_issue_ms() if (world == 1 and graph) else host_ms
+        tr.eager = False
 
-    if rank == 0:
-        images = args.batch * world * args.steps
+    roof = extra = cpu = infer = None
+    if rank == 0 and full:
         avg_ms = d["ms"] / d["n"]
         flops_per = d["flops"] / d["n"]
         bytes_per = d["bytes"] / d["n"]
@@ -913,7 +977,6 @@ def main():
         roof["launches_per_step"] = d["n"] // args.steps
         roof["share_of_step"] = round(d["ms"] / (el_eager * 1e3), 4)
         roof[f"dense_conv_path_b{args.batch}"] = dense_conv_path_median(profs, args.batch)
-        extra = None
         if world == 1 and not (args.no_extra or args.pmc_child):
             del tr
             torch.cuda.empty_cache()
@@ -923,7 +986,6 @@ def main():
         if want_cpu:
             _log("CPU baseline")
         cpu = cpu_baseline(args.cpu_seconds, args.batch, args.size) if want_cpu else None
-        infer = None
         if not (args.no_inference or args.pmc_child) and world == 1:
             _log("sampler measurements")
             infer = inference_bench(dev, args.base_filters)
@@ -931,6 +993,8 @@ def main():
             infer["config1_rdunet64_forward"] = config1_forward(dev)
             _log("RDUNet(128) forward on 1x3x256x256")
             infer["rdunet128_forward_256"] = rdunet128_forward(dev)
+    if rank == 0:
+        images = args.batch * world * args.steps
         out = {
             "metric": "images/sec (256x256x3) RDUNet diffusion train step",
             "value": round(images / el, 2),
@@ -940,7 +1004,8 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": round(el * 1e3 / args.steps, 3),
             "execution": "hipGraph replay per step" if graph else "eager launches",
-            "eager_ms_per_step": round(el_eager * 1e3 / args.steps, 3),
+            "full": full,
+            "eager_ms_per_step": None if el_eager is None else round(el_eager * 1e3 / args.steps, 3),
             "host_issue_ms_per_step": host_ms,
             "eager_host_issue_ms_per_step": host_eager_ms,
             "higher_is_better": True,

@@ -33,6 +33,21 @@ def test_bench_eager_world1():
     assert d["value"] > 0 and d["config"]["parallelism"] == "dp1"
 
 
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """Without --full only the headline is measured (the rest of the line is null) and
+    --dump-outputs writes the last timed step's loss, parameters and gradients."""
+    import numpy as np
+    d = _bench("--gpus", "1", "--dump-outputs", str(tmp_path))
+    assert d["full"] is False and d["steps"] == 2 and d["execution"] == "hipGraph replay per step"
+    assert d["value"] > 0 and abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]
+    assert d["roofline"] is None and d["eager_ms_per_step"] is None and d["host_issue_ms_per_step"] is None
+    out = {n: np.load(tmp_path / f"{n}.npy") for n in ("loss", "params", "grads")}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values())
+    assert out["loss"].shape == (1,) and abs(float(out["loss"][0]) - d["config"]["final_loss"]) <= 1e-5
+    assert out["params"].shape == out["grads"].shape and out["params"].size > 1000
+    assert 0 < np.linalg.norm(out["grads"].astype(np.float64)) <= 1.0 + 1e-3   # (clipped to norm 1)
+
+
 def test_bench_launcher_two_ranks_gloo():
     d = _bench("--gpus", "2", "--one-device", "--dist-backend", "gloo", "--graph", "off")
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 4

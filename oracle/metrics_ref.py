@@ -91,6 +91,60 @@ def ssim_bruteforce(im1: np.ndarray, im2: np.ndarray, data_range: float) -> floa
     return float(np.mean(out))
 
 
+def ssim_windows64(im1: np.ndarray, im2: np.ndarray, data_range: float) -> float:
+    """``ssim_bruteforce`` of one HxW plane with the window loop vectorised (float64,
+    centred two-pass moments per window): for planes where the Python loop is too slow."""
+    from numpy.lib.stride_tricks import sliding_window_view
+    wa = sliding_window_view(np.asarray(im1, dtype=np.float64), (WIN, WIN))
+    wb = sliding_window_view(np.asarray(im2, dtype=np.float64), (WIN, WIN))
+    C1, C2 = (K1 * data_range) ** 2, (K2 * data_range) ** 2
+    n = WIN * WIN
+    ux, uy = wa.mean((-2, -1), keepdims=True), wb.mean((-2, -1), keepdims=True)
+    vx = ((wa - ux) ** 2).sum((-2, -1)) / (n - 1)
+    vy = ((wb - uy) ** 2).sum((-2, -1)) / (n - 1)
+    vxy = ((wa - ux) * (wb - uy)).sum((-2, -1)) / (n - 1)
+    ux, uy = ux[..., 0, 0], uy[..., 0, 0]
+    S = ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2))
+    return float(S.mean())
+
+
+# Near-constant planes far from 0 (a dark SIDD region sits near -1 after Normalize(0.5, 0.5)):
+# E[x^2] - mu^2 cancels to the texture's variance (1e-6) from terms of size 1, and
+# C2 = 3.6e-3 is all that damps an error in it.  Sizes: one full 64-row tile of the GPU kernel
+# plus a short second one (70 rows), two full tiles (134), widths 13 / 16 / 70.
+FLAT_SHAPES = [(70, 13), (70, 16), (134, 13), (70, 70)]
+FLAT_KINDS = ["dark", "bright", "step"]
+FLAT_N = 8
+
+
+def flat_planes(kind: str, h: int, w: int, n: int = FLAT_N):
+    """(gt, x), each [n, 1, h, w] fp32 in [-1, 1]: ``dark`` / ``bright`` = mean -0.97 / +0.95
+    plus 1e-3 N(0,1); ``step`` = the top h // 4 rows uniform(-1, 1), the rest flat at -0.97
+    (plus 1e-3 N(0,1)); x = gt + 1e-3 N(0,1).  One fixed seed per (kind, h, w)."""
+    rng = np.random.default_rng(1000 * h + 10 * w + FLAT_KINDS.index(kind))
+    mean = 0.95 if kind == "bright" else -0.97
+    gt = mean + 1e-3 * rng.standard_normal((n, 1, h, w))
+    if kind == "step":
+        gt[:, :, :h // 4] = rng.uniform(-1, 1, (n, 1, h // 4, w))
+    gt = np.clip(gt, -1, 1).astype(np.float32)
+    x = np.clip(gt + 1e-3 * rng.standard_normal(gt.shape), -1, 1).astype(np.float32)
+    return gt, x
+
+
+_FLAT_REF: dict = {}
+
+
+def flat_planes_ref(kind: str, h: int, w: int, n: int = FLAT_N):
+    """The planes of ``flat_planes`` and each plane's float64 SSIM at data range 2
+    (``ssim_bruteforce``; computed once per process)."""
+    key = (kind, h, w, n)
+    if key not in _FLAT_REF:
+        gt, x = flat_planes(kind, h, w, n)
+        ref = np.array([ssim_bruteforce(g.transpose(1, 2, 0), o.transpose(1, 2, 0), 2.0) for g, o in zip(gt, x)])
+        _FLAT_REF[key] = (gt, x, ref)
+    return _FLAT_REF[key]
+
+
 def batch_metrics(gt: np.ndarray, x: np.ndarray, data_range: float):
     """Per-image (psnr, ssim) of NCHW batches, as evaluate_model computes them per
     block after the CHW -> HWC transpose (evaluate_SIDD.py:59-64)."""

@@ -18,6 +18,28 @@ def test_ssim_matches_bruteforce(shape):
     assert abs(M.ssim(a, b, 2.0, channel_axis=-1) - M.ssim_bruteforce(a, b, 2.0)) < 1e-6
 
 
+@pytest.mark.parametrize("kind", M.FLAT_KINDS)
+@pytest.mark.parametrize("hw", M.FLAT_SHAPES)
+def test_flat_planes_fp32_reference_within_5e6_of_float64(hw, kind):
+    """The inputs of tests/test_gpu_metrics.py::test_flat_planes_match_float64: on exactly
+    those planes the fp32 skimage restatement is within 5e-6 of the float64 window loop, so
+    the GPU test's 2e-5 sits 4x above what the reference arithmetic itself needs.  (Fails
+    if the planes are ever swapped for ones on which that bound is not achievable.)"""
+    gt, x, ref = M.flat_planes_ref(kind, *hw)
+    assert gt.shape == x.shape == (M.FLAT_N, 1, *hw) and gt.dtype == x.dtype == np.float32
+    assert np.abs(gt).max() <= 1 and np.abs(x).max() <= 1
+    assert np.abs(x - gt).max() < 1e-2 and not np.array_equal(gt, x)
+    flat = gt[:, :, hw[0] // 4:] if kind == "step" else gt
+    assert abs(flat.mean() - (0.95 if kind == "bright" else -0.97)) < 1e-3 and flat.std() < 2e-3
+    if kind == "step":
+        assert gt[:, :, :hw[0] // 4].std() > 0.4
+    err = [abs(M.ssim(g[0], o[0], 2.0) - r) for g, o, r in zip(gt, x, ref)]
+    print(f"{hw} {kind}: |fp32 oracle - float64| max {max(err):.2e}")
+    assert max(err) <= 5e-6
+    # the vectorised float64 window loop (the 256^2 plane's reference) is the loop's number
+    assert abs(M.ssim_windows64(gt[0, 0], x[0, 0], 2.0) - ref[0]) < 1e-12
+
+
 def test_closed_forms():
     a = np.full((9, 11, 1), 0.3, np.float32)
     b = np.full((9, 11, 1), -0.2, np.float32)

@@ -51,8 +51,20 @@ ColTiles col_tiles(int w) {
 // t < txo forms the horizontal 7-sums of the five moments (u, v, u^2, v^2, uv) of output
 // column ox0 + t, keeps the last 7 rows of them in registers and a running window sum
 // (add the new row, subtract the one it replaces: 6 VALU per row instead of the 21 of a
-// fresh 7-row sum; fp32 over <= 70 rows, scipy's uniform_filter also slides a running
-// sum); the next 7 rows' loads are in flight meanwhile.
+// fresh 7-row sum); the next 7 rows' loads are in flight meanwhile.
+// The running sums are fp32 (scipy's uniform_filter, the reference's, slides its sum in
+// double), so each update leaves a rounding error of the size of the sum's ulp in them,
+// and it stays for every later row of the column.  uxx - ux^2 then carries it whole: on a
+// near-constant plane far from 0 (sums of squares ~47, variance ~1e-6, only C2 = 3.6e-3
+// damping) 70 rows of drift put a 13..16-wide plane's SSIM 2e-5 .. 7e-5 from float64
+// (measured, tests/test_gpu_metrics.py).  So every 7th row the window sums are formed
+// afresh from the 7 stored rows (+18 VALU per 7 rows; 64 x 3 x 256^2 block pairs: 44 us
+// before and after): the error is that of a fresh fp32 sum plus at most 6 updates,
+// independent per 7-row group, < 1e-5 on those planes and no worse for any other
+// values in [-1, 1].  (A per-block pivot subtracted from both images is exact on a flat
+// plane, but it doubles the magnitudes on a plane that is flat at another level than the
+// pivot's pixel, and the sums below a textured region keep that region's rounding error:
+// 4e-5 on the step planes of the test in a numpy restatement of this loop.)
 // The kernel is VALU-issue bound, so the moments go as packed fp32
 // pairs -- (u, v) and (u^2, v^2) by one v_pk_add_f32 / v_pk_fma_f32 each, in the same
 // per-lane order and rounding as the scalar form -- the SSIM quotient takes one
@@ -136,11 +148,24 @@ __global__ __launch_bounds__(NT_MAX, 5) void image_metrics_kernel(const float* _
             s23 += uv * uv;
             s4 = __builtin_fmaf(uv[0], uv[1], s4);
           }
-          // running 7-row window sums: add row r, drop row r - 7 (the ring slot it replaces)
-          m01 += s01 - h01[k];
-          m23 += s23 - h23[k];
-          m4 += s4 - h4[k];
-          h01[k] = s01; h23[k] = s23; h4[k] = s4;
+          if (k == 0 && r0 > 0) {
+            // every 7th row: the window sums afresh from the 7 stored rows, oldest first
+            // (see above: bounds the running sums' rounding drift to 6 rows)
+            h01[0] = s01; h23[0] = s23; h4[0] = s4;
+            m01 = h01[1]; m23 = h23[1]; m4 = h4[1];
+#pragma unroll
+            for (int j = 2; j <= WIN; ++j) {
+              m01 += h01[j % WIN];
+              m23 += h23[j % WIN];
+              m4 += h4[j % WIN];
+            }
+          } else {
+            // running 7-row window sums: add row r, drop row r - 7 (the ring slot it replaces)
+            m01 += s01 - h01[k];
+            m23 += s23 - h23[k];
+            m4 += s4 - h4[k];
+            h01[k] = s01; h23[k] = s23; h4[k] = s4;
+          }
           const int yo = y - R;                 // output row whose window just completed
           if (r >= 2 * R && ssim_x && yo >= y_lo && yo < y_hi) {
             const f32x2 u = m01 * inv2;                       // (ux, uy)

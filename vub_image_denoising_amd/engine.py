@@ -749,7 +749,11 @@ class UNetEngine:
             # move a whole gradient by ~1/sqrt(pixels): train engines keep the single-pass
             # launches; and a train-mode forward-only call -- the logged loss of a step whose
             # gradient the reference discards, diffusion_RDUnet.forward_step_device -- keeps
-            # the train engine's kernels, so its loss is the train step's bit for bit)
+            # the train engine's kernels, so its loss is the train step's bit for bit.  The
+            # mode is the module's when the engine is built, so _run keeps one forward-only
+            # engine per mode under a shape's key and serves a call from the one whose
+            # module_training equals module.training: an eval call never decides for a
+            # later train-mode call of the same shape, nor the other way round)
             return
         lib = H.lib()
         need = 0
@@ -1344,6 +1348,12 @@ class UNetEngine:
             elif side is not None:
                 side.wait_event(L.extra["ev_ready"])
             if not dw:
+                if fused and batch_side and b >= self.slots and any(Lp is rev[b - self.slots] for Lp, _ in spending):
+                    # a fused wgrad writes its dalpha/dbias partials into this ring slot from
+                    # the side stream and never passes wait_done: the slot's previous layer
+                    # must not still sit in the batch (its reduce reads those partials);
+                    # launched first, the side stream's order does the rest
+                    flush_side()
                 tok = tr.start(info["wgrad"], side) if tr is not None else None
                 rc = lib.rdn_conv_wgrad(C.byref(L.wgrad_desc), sst)
                 if tok is not None:
@@ -1472,10 +1482,15 @@ def _run(module, key_shape, xs, t, params, make_engine):
     key = key_shape + (module.compute_dtype, bool(need_grad))
     pool = module._rdn_engines.setdefault(key, [])
     if not need_grad:
-        if not pool:
-            pool.append(make_engine(False, None))
+        # at most one forward-only engine per module mode (the engine plans split-K from
+        # module.training at construction, _plan_splitk); the first one built stays at [0]
+        training = bool(getattr(module, "training", False))
+        eng = next((e for e in pool if e.module_training == training), None)
+        if eng is None:
+            eng = make_engine(False, None)
+            pool.append(eng)
         with torch.no_grad():
-            return pool[0].forward(xs, t)
+            return eng.forward(xs, t)
     # a graph owns its engine's activations until its backward (or until it is
     # freed): a second forward before that backward gets a second engine, up to
     # MAX_TRAIN_ENGINES per shape; past that the least recently leased engine is

@@ -1,12 +1,15 @@
 """Build ``librdunet_hip.so`` in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["conv_gemm.hip", "conv_pix.hip", "conv3_halo.hip", "conv3_big.hip", "conv3_ws.hip", "conv3_wsd.hip", "conv3_dw.hip", "conv3_dense.hip", "conv3_dense1.hip", "conv_wgrad.hip", "wgrad3_halo.hip", "wgrad3_glds.hip", "pointwise.hip", "synth.hip", "metrics.hip"]
+# every header a translation unit can include (a touched one rebuilds everything)
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "rdunet_hip.h")]
 OUT = os.path.join(HERE, "librdunet_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-command-line-argument"]
@@ -16,10 +19,7 @@ def _stale() -> bool:
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [
-        os.path.join(CSRC, "rdn_common.h"), os.path.join(CSRC, "conv3_tile.h"),
-        os.path.join(HERE, "..", "include", "rdunet_hip.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in [os.path.join(CSRC, s) for s in SOURCES] + HEADERS)
 
 
 def build_library(force: bool = False, verbose: bool = True) -> str:
@@ -30,8 +30,7 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
         return OUT
     objdir = os.path.join(HERE, "..", "build", "obj")
     os.makedirs(objdir, exist_ok=True)
-    hdr_t = max(os.path.getmtime(os.path.join(CSRC, h)) for h in ("rdn_common.h", "conv3_tile.h"))
-    hdr_t = max(hdr_t, os.path.getmtime(os.path.join(HERE, "..", "include", "rdunet_hip.h")))
+    hdr_t = max(os.path.getmtime(h) for h in HEADERS)
     objs = []
     jobs = []
     for s in SOURCES:  # compile translation units in parallel

@@ -34,8 +34,8 @@
 // Packed weights as for conv3_halo (rdn_pack_weights with ck > 0):
 //   P[n][chunk*KC + tap*CK + ci],  KC = roundup(9*CK, 64).
 #include "conv3_tile.h"
-
-#include <cstdlib>
+#include "rdn_device.h"
+#include "rdn_launch.h"
 
 namespace {
 
@@ -46,24 +46,6 @@ __device__ __attribute__((aligned(64))) unsigned int g_big_zero[16];
 // half the epilogue memory instructions (as conv3_dw's dX epilogue), except gate-out.
 // Round 4: the next k-step's fragments are read before the current MFMAs (two fragment
 // sets live; bit-identical; B16 +0.6 %, B32 +0.5 %, profiles/r04_v5_big_pf_gate_out_ab.txt).
-
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// One LDS-DMA wave-instruction: 16 B per lane from `src` to LDS byte dst + lane*16
-// (dst wave-uniform, in M0).  Inline asm, so that the compiler does not treat the
-// LDS as pending on the VM counter (with the builtin it waits vmcnt(0) before every
-// ds_read of the array); the counted waits in the loop are the ordering.
-__device__ __forceinline__ void glds16(const void* src, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(__builtin_amdgcn_readfirstlane(dst))
-               : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)p;
-}
 
 constexpr int TWB = 16;
 constexpr int RS = TWB + 2;        // halo pixels per halo row
@@ -672,22 +654,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3_big_kernel(rdn_conv_desc d, 
 
 int big_mode() {
   // RDN_BIG: unset/"1" = the default shape rule below; "0" = never (conv3_halo)
-  static const int m = [] {
-    const char* e = getenv("RDN_BIG");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return m;
-}
-
-int cu_count() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    cus = n;
-  }
-  return cus;
+  static const bool on = rdn_env_on("RDN_BIG");
+  return on;
 }
 
 int epi_mode(const rdn_conv_desc* d) {
@@ -714,19 +682,14 @@ int launch_pt(const rdn_conv_desc* d, hipStream_t st, int tiles_x, int tiles_y, 
     constexpr bool FWD_ = EP == EP_FWD || EP == EP_FWD_RES;
     if constexpr (!(GO && !FWD_) && Cfg::MT % 2 == 0) {
       // 16-byte epilogue units: 8-channel aligned operands
-      auto a8 = [](int64_t ps, int64_t c0, const void* p) { return ps % 8 == 0 && c0 % 8 == 0 && !((uintptr_t)p & 15); };
-      if (!a8(d->out_ps, d->out_c0, d->out)) return 1;
-      if (FWD_ && !a8(d->pre_ps, 0, d->pre)) return 1;
-      if ((EP == EP_FWD_RES || EP == EP_RES) && (!a8(d->res_ps, d->res_c0, d->res) || d->res_climit % 8)) return 1;
+      if (!rdn_aligned(d->out_ps, d->out_c0, d->out)) return 1;
+      if (FWD_ && !rdn_aligned(d->pre_ps, 0, d->pre)) return 1;
+      if ((EP == EP_FWD_RES || EP == EP_RES) && (!rdn_aligned(d->res_ps, d->res_c0, d->res) || d->res_climit % 8)) return 1;
     }
     if (GO) rdn_probe_rows = (int)((int64_t)d->n * tiles_x * tiles_y * WM);
     RDN_PROBE("conv3_big_kernel<bf16,%d,%d,%d,%d%s%s>", TH, BN, WM, CK, GO ? ",go" : "", NW == 4 ? ",w4" : "");
-    const int per_xcd = (nitems + 7) / 8;
-    int slots = Cfg::BPC * cu_count() / 8;   // blocks per XCD
-    if (slots > per_xcd) slots = per_xcd;
-    if (slots < 1) slots = 1;
-    hipLaunchKernelGGL((conv3_big_kernel<TH, BN, WM, CK, EP, GO, NW>), dim3((unsigned)(8 * slots)), dim3(Cfg::NTB), 0,
-                       st, *d, tiles_x, tiles_y, nitems);
+    hipLaunchKernelGGL((conv3_big_kernel<TH, BN, WM, CK, EP, GO, NW>), dim3((unsigned)rdn_persistent_grid(nitems, Cfg::BPC)),
+                       dim3(Cfg::NTB), 0, st, *d, tiles_x, tiles_y, nitems);
     return rdn_check_launch("rdn_conv_fwd(conv3 big)");
   }
 }
@@ -775,34 +738,25 @@ int launch_big(const rdn_conv_desc* d, hipStream_t st) {
 // 82 -> 74 us per launch, step +0.5 % B16 / +0.4 % B32, profiles/r04_v13_big_ck32_ab.txt).
 // RDN_BIG_CK32=0: single-chunk 32-channel items only (A/B)
 bool big_ck32_multi() {
-  static const bool on = [] {
-    const char* e = getenv("RDN_BIG_CK32");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = rdn_env_on("RDN_BIG_CK32");
   return on;
 }
 
 // RDN_BIG_NW4=0: the 64-column 32-channel-chunk items on 8-wave blocks (A/B)
 bool big_nw4() {
-  static const bool on = [] {
-    const char* e = getenv("RDN_BIG_NW4");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = rdn_env_on("RDN_BIG_NW4");
   return on;
 }
 
 bool big_fall() {
-  static const bool on = [] {
-    const char* e = getenv("RDN_BIG_FALL");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = rdn_env_on("RDN_BIG_FALL");
   return on;
 }
 
 template <int CK>
 int big_dispatch(const rdn_conv_desc* d, hipStream_t st) {
   const int64_t tiles = (int64_t)d->n * ((d->h + 15) / 16) * ((d->w + 15) / 16);
-  const int cus = cu_count(), nch = d->cin / CK;
+  const int cus = rdn_cu_count(), nch = d->cin / CK;
   if (CK == 32 && nch != 1 && !big_ck32_multi()) return 1;
   auto even = [&](int64_t items) {
     const int64_t rounds = (items + cus - 1) / cus;
@@ -817,10 +771,7 @@ int big_dispatch(const rdn_conv_desc* d, hipStream_t st) {
   // us) and so do the 64-column ones (level-2 conv_0..2 forward -1..-2 / -6..-13 us);
   // the 96-column (conv_1 dgrad: even) and 80-column ones (conv_3 dgrad: +4 / +16 us)
   // keep the round-3 rule.  RDN_BIG_LOOSE=0: the round-3 rule everywhere.
-  static const bool loose = [] {
-    const char* e = getenv("RDN_BIG_LOOSE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool loose = rdn_env_on("RDN_BIG_LOOSE");
   auto wide_ok = [&](int bn) {
     const int64_t items = tiles * (d->ncols / bn);
     return even(items) && ((loose && bn == 128) || nch >= 2 || (items >= 4ll * cus && big_img));
@@ -870,19 +821,15 @@ int rdn_conv3_big_launch(const rdn_conv_desc* d, int ck, hipStream_t st) {
   if (ck != 32 && ck != 64) return 1;
   if (epi_mode(d) < 0) return 1;
   if (d->ncols % 16 || d->ncols < 32 || d->cin < 32 || d->ncols > COL_MAX) return 1;
-  if (d->x_ps % 8 || d->x_c0 % 8 || ((uintptr_t)d->x & 15) || ((uintptr_t)d->wp & 15) || d->kp % 8) return 1;
-  if (d->out_ps % 4 || d->out_c0 % 4 || ((uintptr_t)d->out & 7)) return 1;
-  if ((d->flags & RDN_EPI_STORE_PRE) && (d->pre_ps % 4 || ((uintptr_t)d->pre & 7))) return 1;
-  if ((d->flags & RDN_EPI_RESID) && (d->res_ps % 4 || d->res_c0 % 4 || d->res_climit % 4 || ((uintptr_t)d->res & 7)))
-    return 1;
+  if (!rdn_conv_in_aligned(d) || !rdn_aligned(d->out_ps, d->out_c0, d->out, 4)) return 1;
+  if ((d->flags & RDN_EPI_STORE_PRE) && !rdn_aligned(d->pre_ps, 0, d->pre, 4)) return 1;
+  if ((d->flags & RDN_EPI_RESID) && (!rdn_aligned(d->res_ps, d->res_c0, d->res, 4) || d->res_climit % 4)) return 1;
   // grids of at least one item per CU at the 16 x 16 x 128 tile (levels 1-3 of the
   // 256^2 train step and larger)
   const int64_t px = (int64_t)d->n * d->h * d->w;
   if (px < 8192) return 1;
   // 32-bit element offsets (halo) and byte offsets (epilogue, from a per-item base)
-  auto fits = [&](int64_t ps, int64_t pl, int c_hi) {
-    return 2 * ((int64_t)(18 + 1) * d->w * ps + rdn_coff(c_hi, ps, pl)) < (int64_t)RDN_OOB - 16;
-  };
+  auto fits = [&](int64_t ps, int64_t pl, int c_hi) { return rdn_fits32((int64_t)(18 + 1) * d->w, ps, pl, c_hi); };
   if (!fits(d->x_ps, d->x_pl, d->x_c0 + d->cin) || !fits(d->out_ps, d->out_pl, d->out_c0 + d->ncols) ||
       ((d->flags & RDN_EPI_STORE_PRE) && !fits(d->pre_ps, d->pre_pl, d->ncols)) ||
       ((d->flags & RDN_EPI_RESID) && !fits(d->res_ps, d->res_pl, d->res_c0 + d->res_climit)))

@@ -30,7 +30,8 @@
 // (the next conv's padding) -- results are bit-identical to three rdn_conv_fwd
 // launches (tests/test_gpu_dense.py).  The next tile's x loads are in flight in
 // registers while the current tile computes.
-#include "rdn_common.h"
+#include "rdn_device.h"
+#include "rdn_launch.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -72,15 +73,9 @@ using W2 = WCfg<64>;
 
 struct Out { __amdgpu_buffer_rsrc_t o, p; };
 
-// LDS-only barrier: this wave's LDS writes retired, then s_barrier -- NOT
-// __syncthreads(), whose vmcnt(0) would wait for the next tile's x loads and every
-// epilogue store at each of the four barriers of a tile (the first form of this
-// kernel: 115 us per launch without a single MFMA)
-__device__ __forceinline__ void bar_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
+// The barriers are bar_lds() (rdn_device.h), NOT __syncthreads(), whose vmcnt(0) would
+// wait for the next tile's x loads and every epilogue store at each of the four barriers
+// of a tile (the first form of this kernel: 115 us per launch without a single MFMA).
 
 // conv k (input channels CIN of C, output region halo HO: 2, 1, 0) over NMT m-tiles
 // of 16 output-region pixels, MTW = NMT / NW per wave (m-tile wave + NW i); the
@@ -322,13 +317,7 @@ int launch_dense(const rdn_dense3_desc* d, hipStream_t st) {
     return RDN_E_SHAPE;
   }
   RDN_PROBE("conv3_dense_kernel<bf16,32,16,%dx%d>", TH, TW);
-  int dev = 0, cus = 0;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-  int64_t per_xcd = (ntiles + 7) / 8;
-  int slots = cus / 8;
-  if (slots > per_xcd) slots = (int)per_xcd;
-  conv3_dense_kernel<TH, TW><<<8 * slots, NT, 0, st>>>(*d, tiles_x, tiles_y, (int)ntiles);
+  conv3_dense_kernel<TH, TW><<<rdn_persistent_grid(ntiles, 1), NT, 0, st>>>(*d, tiles_x, tiles_y, (int)ntiles);
   return rdn_check_launch("rdn_dense3_fwd");
 }
 

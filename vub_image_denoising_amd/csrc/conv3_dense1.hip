@@ -37,7 +37,8 @@
 // v_permlane32_swap pairs into 16-B units.  Results match the three rdn_conv_fwd
 // launches up to fp32 summation order (bf16-rounded out_0 / out_1 feed the next conv,
 // as the HBM round trip does); tests/test_gpu_dense1.py.
-#include "rdn_common.h"
+#include "rdn_device.h"
+#include "rdn_launch.h"
 
 #include <utility>
 
@@ -89,31 +90,11 @@ constexpr int vm_after(int c) { return stores_n(md(c - 2)) + xdma_n(md(c - 1)) +
 
 __device__ __attribute__((aligned(64))) unsigned int g_dn1_zero[16];
 
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void bar_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-// one LDS-DMA wave-instruction: 16 B per lane from `src` to LDS byte dst + lane * 16
-// (dst wave-uniform, in M0); not counted by the compiler: the explicit vmcnt waits are
-// the ordering
-__device__ __forceinline__ void glds16(const void* src, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(__builtin_amdgcn_readfirstlane(dst))
-               : "memory");
-}
 // opaque copy: keeps loop-invariant address arithmetic inside the tile loop (hoisted,
 // the 21 chunk DMAs' and the epilogues' invariants spilled 328 B/lane)
 __device__ __forceinline__ int opq(int v) {
   asm volatile("" : "+v"(v));
   return v;
-}
-__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)p;
 }
 
 // output-region pixel (y, x) of lane j (0..31) in m-tile m of conv k
@@ -442,12 +423,6 @@ int rdn_dense3_l1_launch(const rdn_dense3_desc* d, hipStream_t st) {
     return RDN_E_SHAPE;
   }
   RDN_PROBE("conv3_dense1_kernel<bf16,64,32,16x16>");
-  int dev = 0, cus = 0;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-  const int64_t per_xcd = (ntiles + 7) / 8;
-  int slots = cus / 8;
-  if (slots > per_xcd) slots = (int)per_xcd;
-  conv3_dense1_kernel<<<8 * slots, NT, 0, st>>>(*d, tiles_x, tiles_y, (int)ntiles);
+  conv3_dense1_kernel<<<rdn_persistent_grid(ntiles, 1), NT, 0, st>>>(*d, tiles_x, tiles_y, (int)ntiles);
   return rdn_check_launch("rdn_dense3_fwd(level 1)");
 }

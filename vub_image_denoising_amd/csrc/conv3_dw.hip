@@ -65,8 +65,8 @@
 // conv_0s (finish down_0 / block_1_k.conv_3: <64,32>, gout_c0 = 0), whose separate
 // PReLU-backward passes (73 / 23 us each at B16) leave the compute queue.
 #include "conv3_tile.h"
-
-#include <stdlib.h>
+#include "rdn_device.h"
+#include "rdn_launch.h"
 
 namespace {
 
@@ -94,22 +94,6 @@ constexpr int DW_WPIPE = 3;   // weight-gradient fragment prefetch depth
 constexpr int LDS_MAX = 160 * 1024;
 
 __device__ __attribute__((aligned(64))) unsigned int g_dw_zero[16];
-
-template <int N>
-__device__ __forceinline__ void dw_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// one LDS-DMA wave-instruction: 16 B per lane from `src` to LDS byte dst + lane*16 (dst
-// wave-uniform, in M0; inline asm, so the compiler does not count it on its waits --
-// the step's explicit vmcnt wait before the barrier is the ordering, as in conv3_big)
-__device__ __forceinline__ void dw_glds16(const void* src, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(__builtin_amdgcn_readfirstlane(dst))
-               : "memory");
-}
-__device__ __forceinline__ unsigned dw_lds_addr(const unsigned char* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)p;
-}
 
 #ifdef DW_STAMPS
 // diagnostic build: per wave, cycles (s_memtime) spent in each phase of the tile loop,
@@ -323,13 +307,13 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
       int oy, ox, on;
       origin(tt, oy, ox, on);
       const bf16* const db = DY + (((int64_t)on * H + (oy - 1)) * W + (ox - 1)) * d.x_ps;
-      const unsigned dst = dw_lds_addr(dyh) + doff;
+      const unsigned dst = lds_addr(dyh) + doff;
 #pragma unroll
       for (int j = 0; j < DPW; ++j) {
         const int pc = rw + 4 * j;
         if (pc >= Cfg::D_PIECES) break;   // wave-uniform
         const void* src = in_img(php[j], oy, ox) ? (const void*)(db + prel[j]) : (const void*)g_dw_zero;
-        dw_glds16(src, dst + pc * 1024);
+        glds16(src, dst + pc * 1024);
       }
     };
     float sa[VEC], sb[VEC];
@@ -624,7 +608,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
         issue_d(t, 0);
         issue_d(min(t + per, t_last), Cfg::D_BYTES);
         load_epi(t, eC);
-        dw_wait_vm<0>();
+        wait_vm<0>();
       } else {
         load(t, lA, gA);
         store(lA, gA, half == 0, 0);
@@ -643,7 +627,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
         load_epi(min(t1, t_last), en);
         dgrad_tile(t, ec, dsel * Cfg::D_BYTES);
         issue_d(min(t + 2 * per, t_last), (dsel == 0 ? 2 : dsel - 1) * Cfg::D_BYTES);
-        dw_wait_vm<2 * NST + Cfg::D_PIECES / 4>();   // tile t1's DMA (issued one step ago) done
+        wait_vm<2 * NST + Cfg::D_PIECES / 4>();   // tile t1's DMA (issued one step ago) done
         __syncthreads();
         dsel = dsel == 2 ? 0 : dsel + 1;
         t = t1;
@@ -677,7 +661,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
       while (step(lA, gA, eC, eN, 0) && step(lA, gA, eN, eC, 1)) {}
     // the last step issued one more DMA (a re-read of the last tile): it must land before
     // the block's LDS is released (or, with partials, re-used below)
-    if constexpr (DDMA) dw_wait_vm<0>();
+    if constexpr (DDMA) wait_vm<0>();
     } else {
     if (t < t_hi) {
       load(t, lA, gA);
@@ -1099,52 +1083,26 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
 }
 
 bool dw_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("RDN_DW");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = rdn_env_on("RDN_DW");
   return on;
-}
-
-int device_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    cus = n;
-  }
-  return cus;
 }
 
 // blocks of the persistent grid = the weight-gradient split count: one per CU (a
 // multiple of 8: the XCD tile ranges), at most the tiles of an XCD's share (per
 // column half: nh halves take nh blocks per XCD slot)
-int dw_grid(int ntiles, int nh = 1) {
-  const int per_xcd = (ntiles + 7) / 8;
-  int slots = device_cus() / (8 * nh);
-  if (slots > per_xcd) slots = per_xcd;
-  if (slots < 1) slots = 1;
-  return 8 * nh * slots;
-}
+int dw_grid(int ntiles, int nh = 1) { return rdn_persistent_grid(ntiles, 1, nh); }
 
 // column halves for this pair: 2 for the 96 / 128-input-channel convs with 32 dY
 // channels (level-1 conv_1 / conv_2), else 1
 // (RDN_DW_HALVES=0: only the single-tile shapes, for A/B)
 bool dw_halves_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("RDN_DW_HALVES");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = rdn_env_on("RDN_DW_HALVES");
   return on;
 }
 int dw_nh(const rdn_conv_desc* d) {
   if (!dw_halves_enabled()) return 1;
   if (d->cin == 32 && (d->ncols == 96 || d->ncols == 128)) return 2;
-  static const bool h5 = [] {   // (RDN_DW_H5=0: the level-1 conv_3 on the separate kernels, for A/B)
-    const char* e = getenv("RDN_DW_H5");
-    return !(e && e[0] == '0');
-  }();
+  static const bool h5 = rdn_env_on("RDN_DW_H5");   // (=0: the level-1 conv_3 on the separate kernels, for A/B)
   if (h5 && d->cin == 64 && d->ncols == 160) return 5;   // level-1 conv_3: five 32-channel parts
   return 1;
 }
@@ -1179,16 +1137,15 @@ bool dw_serves(const rdn_conv_desc* d, const rdn_wgrad_desc* wg) {
   const int nh = dw_nh(d);
   if (d->cin != 16 && d->cin != 32 && !(d->cin == 64 && nh == 5)) return false;
   if (d->ncols != d->cout || d->ncols % 16 || d->ncols < 32 || d->ncols / nh > 80 || wg->ndim != d->ncols) return false;
-  if (wg->mdim > d->cin || wg->mdim <= 0 || wg->b_c0 % 8 || wg->b_ps % 8 || ((uintptr_t)wg->b & 15)) return false;
+  if (wg->mdim > d->cin || wg->mdim <= 0 || !rdn_aligned(wg->b_ps, wg->b_c0, wg->b)) return false;
   // the same gated operand on both sides
   if (wg->a != d->x || wg->a_ps != d->x_ps || wg->a_c0 != d->x_c0 || wg->a_pl != d->x_pl || wg->a_gate != d->gate ||
       wg->a_gate_ps != d->gate_ps || wg->a_gate_pl != d->gate_pl || wg->a_gate_alpha != d->gate_alpha)
     return false;
-  if (d->x_ps % 8 || d->x_c0 % 8 || d->gate_ps % 8 || ((uintptr_t)d->x & 15) || ((uintptr_t)d->gate & 15)) return false;
-  if (((uintptr_t)d->wp & 15) || d->kp % 8 || d->kp < (9 * d->cin + 63) / 64 * 64) return false;
-  if (d->out_ps % 8 || d->out_c0 % 8 || ((uintptr_t)d->out & 15)) return false;
-  if ((d->flags & RDN_EPI_RESID) && (d->res_climit % 8 || d->res_ps % 8 || d->res_c0 % 8 || ((uintptr_t)d->res & 15)))
-    return false;
+  if (!rdn_conv_in_aligned(d) || !rdn_aligned(d->gate_ps, 0, d->gate)) return false;
+  if (d->kp < (9 * d->cin + 63) / 64 * 64) return false;
+  if (!rdn_aligned(d->out_ps, d->out_c0, d->out)) return false;
+  if ((d->flags & RDN_EPI_RESID) && (!rdn_aligned(d->res_ps, d->res_c0, d->res) || d->res_climit % 8)) return false;
   // 32-bit per-thread offsets
   const int64_t span = (int64_t)(TH + 2) * d->w;
   if (span * d->x_ps >= (1ll << 30) || span * wg->b_ps >= (1ll << 30) || span * d->gate_ps >= (1ll << 30) ||

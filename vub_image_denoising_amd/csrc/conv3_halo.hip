@@ -17,8 +17,7 @@
 // Packed weight layout (rdn_pack_weights with ck > 0):
 //   P[n][chunk*KC + tap*CK + ci],  KC = roundup(9*CK, SK),  SK = 128 B / elem.
 #include "conv3_tile.h"
-
-#include <cstdlib>
+#include "rdn_launch.h"
 
 namespace {
 
@@ -29,6 +28,12 @@ using c3::BM;
 using c3::HW_;
 using c3::HaloRow;
 constexpr int ROWB = 160;                  // B-stage row: 128 B + 32 B pad (conflict-free ds_read_b128)
+
+// Can a (T, BN, CK) instantiation pair its K stages at all (the kernel's PAIR)?  bf16 with
+// <= 96 columns and >= 2 stages per chunk.  Where it cannot, PAIR_OK = true would compile
+// the same code as PAIR_OK = false: the launcher takes the `false` one there.
+template <typename T, int BN, int CK>
+constexpr bool can_pair = sizeof(T) == 2 && BN <= 96 && (9 * CK * (int)sizeof(T) + 127) / 128 >= 2;
 
 // occupancy request: narrow tiles keep 2 waves/SIMD, wide tiles let the
 // register allocator use up to 512 VGPRs (measured faster: scripts/kbench.py)
@@ -61,7 +66,7 @@ __global__ __launch_bounds__(NT, (BN >= 64 ? 1 : 2)) void conv3_halo_kernel(rdn_
   // most two blocks per CU: there halving the barriers wins (level-2 forward -11 %,
   // level-1 -17 %), on larger grids the single-stage form's third resident block
   // per CU does (level-2/3 input gradients +10 % when paired)
-  constexpr bool PAIR = PAIR_OK && ES == 2 && BN <= 96 && SPC >= 2;
+  constexpr bool PAIR = PAIR_OK && can_pair<T, BN, CK>;
   constexpr int RW = PAIR ? 288 : ROWB;              // LDS weight row of one (paired) stage
   constexpr int SS = PAIR ? (SPC + 1) / 2 : SPC;     // (paired) stages per chunk
   // WALL (split launches, <= 64 columns): a chunk's SPC weight stages are loaded at once
@@ -466,13 +471,8 @@ int launch_h(const rdn_conv_desc* d, hipStream_t st, int splits = 0, float* ws =
         *d, tiles_x, tiles_y, c_per, ws);
     return rdn_check_launch("rdn_conv_fwd_splitk(conv3)");
   }
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  }
-  const bool pair = blocks <= 2 * (int64_t)cus;
+  constexpr bool CP = can_pair<T, BN, CK>;
+  const bool pair = CP && blocks <= 2 * (int64_t)rdn_cu_count();
   if (d->gout) {
     // gate-out only on the fast epilogue with a fixed channel group per thread
     constexpr int VEC = TypeInfo<T>::VEC;
@@ -488,17 +488,17 @@ int launch_h(const rdn_conv_desc* d, hipStream_t st, int splits = 0, float* ws =
     rdn_probe_rows = (int)(d->n * tiles_x * tiles_y);
   }
   RDN_PROBE("conv3_halo_kernel<%s,%d,%d,%d%s%s>", rdn_tname<T>(), BN, WMW, CK, d->gate ? ",gate" : "",
-            pair && sizeof(T) == 2 && BN <= 96 ? ",pair" : "");
+            pair ? ",pair" : "");
   if (d->gate) {
     if constexpr (NT % (CK / TypeInfo<T>::VEC) == 0) {
-      if (pair) conv3_halo_kernel<T, BN, WMW, CK, true, true><<<grid, NT, 0, st>>>(*d, tiles_x, tiles_y);
+      if (pair) conv3_halo_kernel<T, BN, WMW, CK, true, CP><<<grid, NT, 0, st>>>(*d, tiles_x, tiles_y);
       else conv3_halo_kernel<T, BN, WMW, CK, true, false><<<grid, NT, 0, st>>>(*d, tiles_x, tiles_y);
     } else {
       rdn_set_error("rdn_conv_fwd(conv3): gated input needs a power-of-two channel chunk");
       return RDN_E_SHAPE;
     }
   } else {
-    if (pair) conv3_halo_kernel<T, BN, WMW, CK, false, true><<<grid, NT, 0, st>>>(*d, tiles_x, tiles_y);
+    if (pair) conv3_halo_kernel<T, BN, WMW, CK, false, CP><<<grid, NT, 0, st>>>(*d, tiles_x, tiles_y);
     else conv3_halo_kernel<T, BN, WMW, CK, false, false><<<grid, NT, 0, st>>>(*d, tiles_x, tiles_y);
   }
   return rdn_check_launch("rdn_conv_fwd(conv3)");

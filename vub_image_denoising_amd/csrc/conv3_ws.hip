@@ -22,8 +22,7 @@
 // Same packed layout and epilogue flags as conv3_halo (P[n][tap*CK + ci], KC =
 // roundup(9*CK, 64)); GATE = PReLU backward fused into the halo loader.
 #include "conv3_tile.h"
-
-#include <stdlib.h>
+#include "rdn_launch.h"
 
 namespace {
 
@@ -606,42 +605,22 @@ __global__ __launch_bounds__(NT, 2) void conv3_ws_kernel(rdn_conv_desc d, int ti
   }
 }
 
-int ws_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("RDN_CONV3_WS");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
+bool ws_enabled() {
+  static const bool on = rdn_env_on("RDN_CONV3_WS");
   return on;
 }
 
 // the accumulator epilogue where it applies (RDN_WS_AE=0: the LDS-tile epilogue, for A/B)
 bool ws_ae_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("RDN_WS_AE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = rdn_env_on("RDN_WS_AE");
   return on;
 }
 
-// resident blocks per CU of one instantiation (registers, LDS, waves), from the
-// runtime's occupancy calculator, capped at 4; the persistent grid is sized to it
-template <typename K>
-int resident_per_cu(K kernel, int cap) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, NT, 0) != hipSuccess || n < 1) n = 1;
-  return n < cap ? n : cap;
-}
-
 template <int BN, int CK, bool GATE, bool AE>
-int launch_ws_k(const rdn_conv_desc* d, hipStream_t st, int tiles_x, int tiles_y, int ntiles, int cus) {
+int launch_ws_k(const rdn_conv_desc* d, hipStream_t st, int tiles_x, int tiles_y, int ntiles) {
   auto kern = conv3_ws_kernel<BN, CK, GATE, AE>;
-  static const int bpc = resident_per_cu(kern, 4);   // persistent blocks per CU: what is resident
-  const int per_xcd = (ntiles + 7) / 8;
-  int slots = cus * bpc / 8;
-  if (slots > per_xcd) slots = per_xcd;
-  if (slots < 1) slots = 1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(8 * slots)), dim3(NT), 0, st, *d, tiles_x, tiles_y, ntiles);
+  static const int bpc = resident_per_cu(kern, NT, 4);   // persistent blocks per CU: what is resident
+  hipLaunchKernelGGL(kern, dim3((unsigned)rdn_persistent_grid(ntiles, bpc)), dim3(NT), 0, st, *d, tiles_x, tiles_y, ntiles);
   return rdn_check_launch("rdn_conv_fwd(conv3 ws)");
 }
 
@@ -656,57 +635,41 @@ int launch_ws(const rdn_conv_desc* d, hipStream_t st) {
     if (nt >= (1ll << 31)) return 1;
     const int ntiles = (int)nt;
     {   // byte offsets of the tile-relative buffer loads stay below RDN_OOB
-      const int64_t span = (int64_t)(TH + 2) * d->w;
-      auto fits = [&](int64_t ps, int64_t pl, int c_hi) {
-        return 2 * (span * ps + rdn_coff(c_hi, ps, pl)) < (int64_t)RDN_OOB - 16;
-      };
+      auto fits = [&](int64_t ps, int64_t pl, int c_hi) { return rdn_fits32((int64_t)(TH + 2) * d->w, ps, pl, c_hi); };
       if (!fits(d->x_ps, d->x_pl, d->x_c0 + d->cin) || (d->gate && !fits(d->gate_ps, d->gate_pl, d->cin)) ||
           ((d->flags & RDN_EPI_RESID) && d->res && !fits(d->res_ps, d->res_pl, d->res_c0 + d->ncols)) ||
           (d->out && !fits(d->out_ps, d->out_pl, d->out_c0 + d->ncols)))
         return 1;
     }
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    static int cached_cus = 0;
-    if (!cached_cus) {
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-      cached_cus = cus;
-    }
-    cus = cached_cus;
     constexpr int HU = CK / 8;
     if (d->gate && NT % HU != 0) return 1;
     // accumulator epilogue: full tiles, NHWC 4-channel groups, 8-byte aligned operands
-    const int64_t span = (int64_t)TH * d->w;
-    constexpr bool w16 = BN <= 64;
-    auto ok4 = [](int64_t ps, int64_t c0, const void* p) {   // (w16: 16-byte units of 8 channels)
-      return w16 ? (ps % 8 == 0 && c0 % 8 == 0 && !((uintptr_t)p & 15)) : (ps % 4 == 0 && c0 % 4 == 0 && !((uintptr_t)p & 7));
-    };
-    auto fit = [&](int64_t ps, int64_t pl, int c_hi) {
-      return 2 * (span * ps + rdn_coff(c_hi, ps, pl)) < (int64_t)RDN_OOB - 16;
-    };
+    constexpr int ECH = BN <= 64 ? 8 : 4;   // epilogue unit: 16 bytes of 8 channels, else 8 of 4
+    auto ok4 = [](int64_t ps, int64_t c0, const void* p) { return rdn_aligned(ps, c0, p, ECH); };
+    auto fit = [&](int64_t ps, int64_t pl, int c_hi) { return rdn_fits32((int64_t)TH * d->w, ps, pl, c_hi); };
     // (the gated 96-column accumulator-epilogue instantiation spilled: LDS-tile epilogue there)
-    const bool ae = ws_ae_enabled() && !(d->gate && BN > 80) && d->h % TH == 0 && d->w % TW == 0 && d->ncols % (w16 ? 8 : 4) == 0 &&
+    const bool ae = ws_ae_enabled() && !(d->gate && BN > 80) && d->h % TH == 0 && d->w % TW == 0 && d->ncols % ECH == 0 &&
                     !(d->flags & RDN_EPI_OUT_NCHW) && ok4(d->out_ps, d->out_c0, d->out) &&
                     fit(d->out_ps, d->out_pl, d->out_c0 + d->ncols) &&
                     (!(d->flags & RDN_EPI_STORE_PRE) || (ok4(d->pre_ps, 0, d->pre) && fit(d->pre_ps, d->pre_pl, d->ncols))) &&
                     (!(d->flags & RDN_EPI_RESID) ||
-                     (ok4(d->res_ps, d->res_c0, d->res) && d->res_climit % (w16 ? 8 : 4) == 0 &&
+                     (ok4(d->res_ps, d->res_c0, d->res) && d->res_climit % ECH == 0 &&
                       fit(d->res_ps, d->res_pl, d->res_c0 + d->ncols)));
     RDN_PROBE("conv3_ws_kernel<bf16,%d,%d%s%s>", BN, CK, d->gate ? ",gate" : "", ae ? ",ae" : "");
     if (d->gate) {
       if constexpr (NT % HU == 0) {
         if constexpr (BN > 80) {
-          return launch_ws_k<BN, CK, true, false>(d, st, tiles_x, tiles_y, ntiles, cus);
+          return launch_ws_k<BN, CK, true, false>(d, st, tiles_x, tiles_y, ntiles);
         } else {
-          return ae ? launch_ws_k<BN, CK, true, true>(d, st, tiles_x, tiles_y, ntiles, cus)
-                    : launch_ws_k<BN, CK, true, false>(d, st, tiles_x, tiles_y, ntiles, cus);
+          return ae ? launch_ws_k<BN, CK, true, true>(d, st, tiles_x, tiles_y, ntiles)
+                    : launch_ws_k<BN, CK, true, false>(d, st, tiles_x, tiles_y, ntiles);
         }
       } else {
         return 1;
       }
     }
-    return ae ? launch_ws_k<BN, CK, false, true>(d, st, tiles_x, tiles_y, ntiles, cus)
-              : launch_ws_k<BN, CK, false, false>(d, st, tiles_x, tiles_y, ntiles, cus);
+    return ae ? launch_ws_k<BN, CK, false, true>(d, st, tiles_x, tiles_y, ntiles)
+              : launch_ws_k<BN, CK, false, false>(d, st, tiles_x, tiles_y, ntiles);
   }
 }
 
@@ -728,7 +691,7 @@ int ws_bn(const rdn_conv_desc* d, hipStream_t st) {
 // 0 = launched, < 0 = error, 1 = shape not served here (caller uses conv3_halo)
 int rdn_conv3_ws_launch(const rdn_conv_desc* d, int ck, hipStream_t st) {
   if (!ws_enabled() || d->dtype != RDN_BF16 || d->bn || ck != d->cin || d->ncols > 96 || d->gout) return 1;
-  if (d->x_ps % 8 || d->x_c0 % 8 || ((uintptr_t)d->x & 15) || ((uintptr_t)d->wp & 15) || d->kp % 8) return 1;
+  if (!rdn_conv_in_aligned(d)) return 1;
   switch (ck) {
     case 8: return ws_bn<8>(d, st);
     case 16: return ws_bn<16>(d, st);

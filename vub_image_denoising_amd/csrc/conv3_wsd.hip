@@ -9,17 +9,16 @@
 //
 //   waves 0-3 (MMA): own the LDS-DMA halo ring.  Per tile they wait for their own
 //     DMAs (counted `s_waitcnt vmcnt`), publish with a raw s_barrier, issue the DMA
-//     of the tile NS-1 ahead, apply the fused PReLU-backward gate in LDS (GATE: the
-//     saved PReLU input arrives by DMA beside dY), run the 9 taps x MFMA against the
-//     resident weight panel and write the fp32 tile to the LDS epilogue buffer.
+//     of the tile NS-1 ahead, run the 9 taps x MFMA against the resident weight panel
+//     and write the fp32 tile to the LDS epilogue buffer.
 //   waves 4-7 (epilogue): meanwhile finish the PREVIOUS tile from that buffer: bias,
 //     PReLU-input store, PReLU, residual / accumulate operand (prefetched one tile
 //     ahead into registers), 16-byte NHWC stores.
 //
 // The MMA waves issue no other vector-memory instruction, so their vmcnt counts
 // only DMAs and the ring stays in flight across the barriers; the epilogue waves'
-// loads and stores are ordinary compiler-tracked memory operations.  DMAs are inline
-// asm (the builtin makes the compiler wait vmcnt(0) before LDS reads of the array).
+// loads and stores are ordinary compiler-tracked memory operations (rdn_device.h:
+// glds16 on why the DMA is inline asm).
 //
 // Halo image: dense rows of CK*2 bytes (a DMA wave-instruction fills 1 KiB
 // contiguously); the ds_read_b128 fragment reads (16 consecutive pixels x 64 B) are
@@ -29,10 +28,12 @@
 //
 // Same packed weights (P[n][tap*CK + ci], KC = roundup(9*CK, 64)) and epilogue
 // flags as conv3_ws / conv3_halo; only full 8 x 16 tiles with 16-byte NHWC units
-// take this path (the launcher checks).
+// take this path (the launcher checks), and only the ungated shapes of wsd_serves
+// are compiled: a gated form (the PReLU backward applied to the halo in LDS) lost to
+// conv3_ws beside the weight-gradient stream and was removed.
 #include "conv3_tile.h"
-
-#include <stdlib.h>
+#include "rdn_device.h"
+#include "rdn_launch.h"
 
 namespace {
 
@@ -56,7 +57,7 @@ __device__ __forceinline__ int rot(int x) {
   else return 0;                                       // 8, 48, 80: conflict-free unrotated
 }
 
-template <int BN, int CK, bool GATE>
+template <int BN, int CK>
 struct WsdCfg {
   static constexpr int U = CK / 8;                     // 16-B units per halo pixel
   static constexpr int RB = CK * 2;
@@ -65,51 +66,39 @@ struct WsdCfg {
   static constexpr int WROW = KC * 2 + 32;             // = 32 mod 128: conflict-free B reads
   static constexpr int W_BYTES = BN * WROW;
   static constexpr int HPC = (HW_ * RB + 1023) / 1024; // 1-KiB DMA pieces per halo
-  static constexpr int STAGE = (GATE ? 2 : 1) * HPC * 1024;
+  static constexpr int STAGE = HPC * 1024;
   static constexpr int CROWF = BN + 4;                 // epilogue fp32 row (floats)
   static constexpr int CT_BYTES = BM * CROWF * 4;
-  static constexpr int AL_BYTES = GATE ? (CK * 4 + 15) / 16 * 16 : 0;
-  static constexpr int FIXED = W_BYTES + CT_BYTES + AL_BYTES;
+  static constexpr int FIXED = W_BYTES + CT_BYTES;
   static constexpr int NS = FIXED + 3 * STAGE <= LDS_MAX ? 3 : 2;
   static constexpr int LDS = FIXED + NS * STAGE;
   static constexpr bool FITS = LDS <= LDS_MAX && BN <= 80;   // 96 columns spill (fallback: conv3_ws)
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void barrier() {
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
+// The shapes served (BN = columns rounded up to 16, CK = input channels): where this
+// kernel beats conv3_ws (per-layer A/B on the train step, r02) -- the forward convs with
+// 96-channel inputs (level-1 conv_1 46 -> 32 us, up_0 123 -> 112 us) and the 64 -> 32
+// level-1 forward; elsewhere conv3_ws's 2-3 resident blocks per CU hide more latency.
+// The one rule for what is compiled and what is dispatched: launch_wsd returns 1 for
+// every other shape and instantiates no kernel for it.
+template <int BN, int CK>
+constexpr bool wsd_serves = (CK == 96 || (BN == 32 && CK == 64)) && WsdCfg<BN, CK>::FITS;
 
-// one LDS-DMA wave-instruction: 16 B per lane from src to LDS byte dst + lane*16
-__device__ __forceinline__ void glds16(const void* src, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(__builtin_amdgcn_readfirstlane(dst))
-               : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)p;
-}
-
-// DMAs a wave issues per tile: pieces wave, wave+4, ... < HPC (x2 with the gate)
-template <int HPC, int MULT>
+// DMAs a wave issues per tile: pieces wave, wave+4, ... < HPC
+template <int HPC>
 __device__ __forceinline__ void wait_own(int wave, bool one_ahead) {
   if (!one_ahead) { wait_vm<0>(); return; }
   switch (wave) {
-    case 0: wait_vm<MULT * ((HPC + 3) / 4)>(); break;
-    case 1: wait_vm<MULT * ((HPC + 2) / 4)>(); break;
-    case 2: wait_vm<MULT * ((HPC + 1) / 4)>(); break;
-    default: wait_vm<MULT * (HPC / 4)>(); break;
+    case 0: wait_vm<(HPC + 3) / 4>(); break;
+    case 1: wait_vm<(HPC + 2) / 4>(); break;
+    case 2: wait_vm<(HPC + 1) / 4>(); break;
+    default: wait_vm<HPC / 4>(); break;
   }
 }
 
-template <int BN, int CK, bool GATE>
+template <int BN, int CK>
 __global__ __launch_bounds__(NTH, 1) void conv3_wsd_kernel(rdn_conv_desc d, int tiles_x, int tiles_y, int ntiles) {
-  using Cfg = WsdCfg<BN, CK, GATE>;
+  using Cfg = WsdCfg<BN, CK>;
   constexpr int U = Cfg::U, RB = Cfg::RB, KC = Cfg::KC, WROW = Cfg::WROW, NSTEP = Cfg::NSTEP, NS = Cfg::NS;
   constexpr int HPC = Cfg::HPC, CROWF = Cfg::CROWF;
   constexpr int HPW = (HPC + 3) / 4;                   // max pieces per wave
@@ -117,13 +106,12 @@ __global__ __launch_bounds__(NTH, 1) void conv3_wsd_kernel(rdn_conv_desc d, int 
   constexpr int VEC = 8;
   constexpr int UPR = BN / VEC, EU = BM * UPR, E_IT = (EU + 255) / 256;
   constexpr bool COLFIX = 256 % UPR == 0;
-  static_assert(Cfg::FITS, "LDS");
+  static_assert(wsd_serves<BN, CK>, "shape");
 
   __shared__ __attribute__((aligned(1024))) unsigned char lds[Cfg::LDS];
   unsigned char* const ring = lds;                                   // NS x STAGE
   unsigned char* const wl = lds + NS * Cfg::STAGE;                   // resident weights
   float* const Ct = (float*)(wl + Cfg::W_BYTES);                     // epilogue tile
-  float* const alds = (float*)(wl + Cfg::W_BYTES + Cfg::CT_BYTES);   // gate slopes
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool mma = wave < 4;
@@ -146,7 +134,7 @@ __global__ __launch_bounds__(NTH, 1) void conv3_wsd_kernel(rdn_conv_desc d, int 
     on = tt / tiles_y;
   };
 
-  // ---- resident weights (and gate slopes), plain loads, once
+  // ---- resident weights, plain loads, once
   {
     const bf16* __restrict__ WP = (const bf16*)d.wp;
     constexpr int UPRW = KC / VEC;
@@ -154,17 +142,14 @@ __global__ __launch_bounds__(NTH, 1) void conv3_wsd_kernel(rdn_conv_desc d, int 
       const int n = u / UPRW, k8 = u - n * UPRW;
       *(u32x4*)(wl + n * WROW + k8 * 16) = *(const u32x4*)(WP + (int64_t)n * d.kp + k8 * VEC);
     }
-    if constexpr (GATE)
-      for (int c = tid; c < CK; c += NTH) alds[c] = d.gate_alpha[c];
   }
   __syncthreads();   // nothing in flight yet
 
   const bf16* __restrict__ X = (const bf16*)d.x;
-  const bf16* __restrict__ Gp = (const bf16*)d.gate;
   const bf16* const zero = (const bf16*)g_wsd_zero;
 
   // ================= MMA waves: DMA geometry, fragment offsets
-  int h_rel[HPW], g_rel[GATE ? HPW : 1], h_y[HPW], h_x[HPW];
+  int h_rel[HPW], h_y[HPW], h_x[HPW];
   bool h_row[HPW];
   int offA[NSTEP];
   if (mma) {
@@ -177,7 +162,6 @@ __global__ __launch_bounds__(NTH, 1) void conv3_wsd_kernel(rdn_conv_desc d, int 
       h_y[j] = hy;
       h_x[j] = hx;
       h_rel[j] = (hy * W + hx) * (int)d.x_ps + rdn_coff32(d.x_c0 + u * VEC, (int)d.x_ps, (int)d.x_pl);
-      if constexpr (GATE) g_rel[j] = (hy * W + hx) * (int)d.gate_ps + rdn_coff32(u * VEC, (int)d.gate_ps, (int)d.gate_pl);
     }
     // lane (r, g) of k-step j: pixel r of tile rows 2*wave (+1), k = 32 j + 8 g
 #pragma unroll
@@ -196,7 +180,6 @@ __global__ __launch_bounds__(NTH, 1) void conv3_wsd_kernel(rdn_conv_desc d, int 
     origin(i, y0, x0, nimg);
     const int64_t hpix0 = ((int64_t)nimg * H + (y0 - 1)) * W + (x0 - 1);
     const bf16* const xb = X + hpix0 * d.x_ps;
-    const bf16* const gb = GATE ? Gp + hpix0 * d.gate_ps : nullptr;
     const bool interior = y0 >= 1 && y0 + TH + 1 <= H && x0 >= 1 && x0 + TW + 1 <= W;
     const unsigned st = lds_addr(ring) + (i % NS) * Cfg::STAGE;
 #pragma unroll
@@ -205,8 +188,6 @@ __global__ __launch_bounds__(NTH, 1) void conv3_wsd_kernel(rdn_conv_desc d, int 
       const bool ok = h_row[j] & (interior | (((unsigned)(y0 - 1 + h_y[j]) < (unsigned)H) &
                                               ((unsigned)(x0 - 1 + h_x[j]) < (unsigned)W)));
       glds16(ok ? (const void*)(xb + h_rel[j]) : (const void*)zero, st + (wave + 4 * j) * 1024);
-      if constexpr (GATE)
-        glds16(ok ? (const void*)(gb + g_rel[j]) : (const void*)zero, st + (HPC + wave + 4 * j) * 1024);
     }
   };
 
@@ -299,32 +280,10 @@ __global__ __launch_bounds__(NTH, 1) void conv3_wsd_kernel(rdn_conv_desc d, int 
   }
   for (int i = 0; i <= cnt; ++i) {
     f32x4 acc[MT][NTL];
-    if (mma && i < cnt) wait_own<HPC, GATE ? 2 : 1>(wave, NS == 3 && i + 1 < cnt);   // own DMAs of tile i landed
-    wait_lgkm0();                                    // Ct writes of tile i-1 done
-    barrier();                                       // A: stage i complete; stage i-1 and Ct(i-1) released
+    if (mma && i < cnt) wait_own<HPC>(wave, NS == 3 && i + 1 < cnt);   // own DMAs of tile i landed
+    bar_lds();   // A: Ct writes of tile i-1 done, stage i complete; stage i-1 and Ct(i-1) released
     const unsigned char* const st = ring + (i % NS) * Cfg::STAGE;
     if (mma && i + NS - 1 < cnt) issue(i + NS - 1);
-    if constexpr (GATE) {
-      if (mma && i < cnt) {   // dY <- dY * (pre > 0 ? 1 : alpha) in place, slot by slot
-        unsigned char* const hs = ring + (i % NS) * Cfg::STAGE;
-        for (int k = tid; k < HW_ * U; k += 256) {
-          const int hr = k / U, ps = k - hr * U;
-          const int u = (ps - rot<CK>(hr % (TW + 2)) + U) % U;
-          float dy[VEC], pr[VEC];
-          Unit16<bf16>::unpack(*(const u32x4*)(hs + k * 16), dy);
-          Unit16<bf16>::unpack(*(const u32x4*)(hs + HPC * 1024 + k * 16), pr);
-          const f32x4 a0 = *(const f32x4*)(alds + u * VEC), a1 = *(const f32x4*)(alds + u * VEC + 4);
-#pragma unroll
-          for (int q = 0; q < VEC; ++q) {
-            const float a = q < 4 ? a0[q] : a1[q - 4];
-            dy[q] = pr[q] > 0.f ? dy[q] : a * dy[q];
-          }
-          *(u32x4*)(hs + k * 16) = Unit16<bf16>::pack(dy);
-        }
-      }
-      wait_lgkm0();
-      barrier();                                     // G: gated halo visible
-    }
     if (mma && i < cnt) {
 #pragma unroll
       for (int a = 0; a < MT; ++a)
@@ -359,8 +318,7 @@ __global__ __launch_bounds__(NTH, 1) void conv3_wsd_kernel(rdn_conv_desc d, int 
       if (i >= 1) epilogue(i - 1);
       if (i < cnt && (has_res || has_acc)) prefetch(i);
     }
-    wait_lgkm0();
-    barrier();                                       // B: Ct(i-1) consumed
+    bar_lds();                                       // B: Ct(i-1) consumed
     if (mma && i < cnt) {
 #pragma unroll
       for (int a = 0; a < MT; ++a)
@@ -372,41 +330,20 @@ __global__ __launch_bounds__(NTH, 1) void conv3_wsd_kernel(rdn_conv_desc d, int 
   }
 }
 
-template <typename K>
-int resident_per_cu(K kernel) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, NTH, 0) != hipSuccess || n < 1) n = 1;
-  return n < 2 ? n : 2;
-}
-
 template <int BN, int CK>
 int launch_wsd(const rdn_conv_desc* d, hipStream_t st) {
-  const bool gate = d->gate != nullptr;
-  const int tiles_x = d->w / TW, tiles_y = d->h / TH;
-  const int64_t nt = (int64_t)d->n * tiles_x * tiles_y;
-  if (nt >= (1ll << 31)) return 1;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  }
-  auto run = [&](auto kern, const char* tag) -> int {
-    RDN_PROBE("conv3_wsd_kernel<bf16,%d,%d%s>", BN, CK, tag);
-    static const int bpc = resident_per_cu(kern);
-    const int per_xcd = (int)((nt + 7) / 8);
-    int slots = cus * bpc / 8;
-    if (slots > per_xcd) slots = per_xcd;
-    if (slots < 1) slots = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(8 * slots)), dim3(NTH), 0, st, *d, tiles_x, tiles_y, (int)nt);
-    return rdn_check_launch("rdn_conv_fwd(conv3 wsd)");
-  };
-  if (gate) {
-    if constexpr (WsdCfg<BN, CK, true>::FITS) return run(conv3_wsd_kernel<BN, CK, true>, ",gate");
+  if constexpr (!wsd_serves<BN, CK>) {
     return 1;
+  } else {
+    const int tiles_x = d->w / TW, tiles_y = d->h / TH;
+    const int64_t nt = (int64_t)d->n * tiles_x * tiles_y;
+    if (nt >= (1ll << 31)) return 1;
+    RDN_PROBE("conv3_wsd_kernel<bf16,%d,%d>", BN, CK);
+    auto kern = conv3_wsd_kernel<BN, CK>;
+    static const int bpc = resident_per_cu(kern, NTH, 2);
+    hipLaunchKernelGGL(kern, dim3((unsigned)rdn_persistent_grid(nt, bpc)), dim3(NTH), 0, st, *d, tiles_x, tiles_y, (int)nt);
+    return rdn_check_launch("rdn_conv_fwd(conv3 wsd)");
   }
-  if constexpr (WsdCfg<BN, CK, false>::FITS) return run(conv3_wsd_kernel<BN, CK, false>, "");
-  return 1;
 }
 
 template <int CK>
@@ -426,28 +363,19 @@ int wsd_bn(const rdn_conv_desc* d, hipStream_t st) {
 
 // 0 = launched, < 0 = error, 1 = not served here (caller falls back to conv3_ws)
 int rdn_conv3_wsd_launch(const rdn_conv_desc* d, int ck, hipStream_t st) {
-  static const bool off = [] {
-    const char* e = getenv("RDN_CONV3_WSD");
-    return e && e[0] == '0';
-  }();
-  if (off || d->dtype != RDN_BF16 || d->bn || ck != d->cin || d->ncols > 96 || d->ncols % 8 || d->gout) return 1;
-  // where it beats conv3_ws (per-layer A/B on the train step, r02): the forward
-  // convs with 96-channel inputs (level-1 conv_1 46 -> 32 us, up_0 123 -> 112 us)
-  // and the 64 -> 32 level-1 forward; elsewhere conv3_ws's 2-3 resident blocks per
-  // CU hide more latency, and the gated input gradients (80 columns: 138 -> 128 us
-  // alone) lost it again beside the weight-gradient stream
-  const int bn16 = (d->ncols + 15) / 16 * 16;
-  if (d->gate || !(ck == 96 || (bn16 == 32 && ck == 64))) return 1;
+  static const bool on = rdn_env_on("RDN_CONV3_WSD");
+  if (!on || d->dtype != RDN_BF16 || d->bn || ck != d->cin || d->ncols > 96 || d->ncols % 8 || d->gout) return 1;
+  // (the gated input gradients, 80 columns: 138 -> 128 us alone, lost it again beside
+  // the weight-gradient stream)
+  if (d->gate) return 1;
   if (d->h % TH || d->w % TW) return 1;                          // full tiles only
   const int flags = d->flags;
   if (flags & (RDN_EPI_OUT_NCHW | RDN_EPI_SCATTER2)) return 1;
-  if ((flags & RDN_EPI_RESID) && (d->res_climit % 8 || d->res_ps % 8 || d->res_c0 % 8 || ((uintptr_t)d->res & 15)))
-    return 1;
-  if (d->out_ps % 8 || d->out_c0 % 8 || ((uintptr_t)d->out & 15)) return 1;
-  if ((flags & RDN_EPI_STORE_PRE) && (d->pre_ps % 8 || ((uintptr_t)d->pre & 15))) return 1;
-  if (d->x_ps % 8 || d->x_c0 % 8 || ((uintptr_t)d->x & 15) || ((uintptr_t)d->wp & 15) || d->kp % 8) return 1;
-  if (d->gate && (d->gate_ps % 8 || ((uintptr_t)d->gate & 15))) return 1;
-  switch (ck) {
+  if ((flags & RDN_EPI_RESID) && (!rdn_aligned(d->res_ps, d->res_c0, d->res) || d->res_climit % 8)) return 1;
+  if (!rdn_aligned(d->out_ps, d->out_c0, d->out)) return 1;
+  if ((flags & RDN_EPI_STORE_PRE) && !rdn_aligned(d->pre_ps, 0, d->pre)) return 1;
+  if (!rdn_conv_in_aligned(d)) return 1;
+  switch (ck) {   // (wsd_serves: most of these return 1)
     case 8: return wsd_bn<8>(d, st);
     case 16: return wsd_bn<16>(d, st);
     case 32: return wsd_bn<32>(d, st);

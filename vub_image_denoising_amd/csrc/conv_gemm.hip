@@ -18,8 +18,7 @@
 // of the next stage.  bf16: v_mfma_f32_16x16x32_bf16, fp32: v_mfma_f32_16x16x4_f32
 // (exact fp32, the mode parity is checked in).
 #include "conv3_tile.h"
-
-#include <cstdlib>
+#include "rdn_launch.h"
 
 namespace {
 
@@ -355,10 +354,7 @@ int launch_typed(const rdn_conv_desc* d, hipStream_t st, int splits = 0, float* 
 }  // namespace
 
 // A/B switch of conv_pix.hip (RDN_PIX=0: the 2x2 shapes stay on conv_gemm_kernel)
-static const bool RDN_PIX = [] {
-  const char* e = getenv("RDN_PIX");
-  return !(e && e[0] == '0');
-}();
+static const bool RDN_PIX = rdn_env_on("RDN_PIX");   // (read when the library loads)
 
 extern "C" int rdn_conv_fwd(const rdn_conv_desc* d, void* stream) {
   if (!d || !d->x || !d->wp) { rdn_set_error("rdn_conv_fwd: null descriptor/pointer"); return RDN_E_ARG; }
@@ -487,20 +483,6 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(rdn_conv_desc d
   c3::finish_unit<T>(d, v, c, opix, y, x, nimg, c3::PF_NONE, u32x4{0u, 0u, 0u, 0u});
 }
 
-// the split rule's CU count (~2 blocks per CU as the target: 4 and 8 per CU measured the
-// same on config 1's graph forward, 1.22 ms, r06)
-int device_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, c = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        c <= 0)
-      c = 256;
-    cus = c;
-  }
-  return cus;
-}
-
 // slices of a 2x2 / per-pixel GEMM layer: as the 3x3 rule (conv3_halo.hip), over K stages
 int gemm_splitk_slices(const rdn_conv_desc* d, int cus) {
   if (d->gather == RDN_G_CONV3 || d->gate || d->gout || d->ncols % 4) return 0;
@@ -517,9 +499,11 @@ int gemm_splitk_slices(const rdn_conv_desc* d, int cus) {
   return (nst + s_per - 1) / s_per;
 }
 
+// (the split rules go by the CU count, ~2 blocks per CU as the target: 4 and 8 per CU
+// measured the same on config 1's graph forward, 1.22 ms, r06)
 int splitk_slices(const rdn_conv_desc* d) {
   if (d->dtype != RDN_F32 && d->dtype != RDN_BF16) return 0;
-  return d->gather == RDN_G_CONV3 ? rdn_conv3_splitk_slices(d, device_cus()) : gemm_splitk_slices(d, device_cus());
+  return d->gather == RDN_G_CONV3 ? rdn_conv3_splitk_slices(d, rdn_cu_count()) : gemm_splitk_slices(d, rdn_cu_count());
 }
 
 }  // namespace

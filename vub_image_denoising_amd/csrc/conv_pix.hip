@@ -25,7 +25,7 @@
 // swapped (D = W x^T instead of x W^T): every output element is the same 32-term
 // dot products accumulated in the same k-step order (bit-identical results,
 // tests/test_gpu_pix.py).
-#include "rdn_common.h"
+#include "rdn_launch.h"
 
 namespace {
 
@@ -187,13 +187,7 @@ int launch_pix(const rdn_conv_desc* d, hipStream_t st) {
   const int64_t M = (int64_t)d->n * d->h * d->w;
   const int ncs = d->ncols / (16 * CT);
   const int64_t groups = (M + 31) / 32;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-      cus = 256;
-  }
+  const int cus = rdn_cu_count();
   // persistent: as many waves as are resident (a stream = ncs waves)
   static int bpc[2] = {0, 0};
   int& res = bpc[d->gather == RDN_G_S2];
@@ -230,12 +224,11 @@ int rdn_conv_pix_launch(const rdn_conv_desc* d, hipStream_t st) {
   if (d->bm || d->bn) return 1;
   const int taps = d->gather == RDN_G_S2 ? 4 : 1;
   const int K = taps * d->cin;
-  if (d->cin % 8 || d->ncols % 64 || d->x_ps % 8 || d->x_c0 % 8 || d->out_ps % 8 || d->out_c0 % 8 || d->kp < K ||
-      ((uintptr_t)d->x & 15) || ((uintptr_t)d->wp & 15) || ((uintptr_t)d->out & 15))
+  if (d->cin % 8 || d->ncols % 64 || d->kp < K || !rdn_aligned(d->x_ps, d->x_c0, d->x) || ((uintptr_t)d->wp & 15) ||
+      !rdn_aligned(d->out_ps, d->out_c0, d->out))
     return 1;
-  if ((d->flags & RDN_EPI_STORE_PRE) && (d->pre_ps % 8 || ((uintptr_t)d->pre & 15))) return 1;
-  if ((d->flags & RDN_EPI_RESID) && (d->res_ps % 8 || d->res_c0 % 8 || d->res_climit % 8 || ((uintptr_t)d->res & 15)))
-    return 1;
+  if ((d->flags & RDN_EPI_STORE_PRE) && !rdn_aligned(d->pre_ps, 0, d->pre)) return 1;
+  if ((d->flags & RDN_EPI_RESID) && (!rdn_aligned(d->res_ps, d->res_c0, d->res) || d->res_climit % 8)) return 1;
   if ((d->flags & RDN_EPI_SCATTER2) && (d->cout % 16 || d->cout * 4 != d->ncols)) return 1;
   if ((int64_t)d->n * d->h * d->w >= (1ll << 31)) return 1;
   // Where it runs (per-layer A/B against conv_gemm_kernel in the B16 train step, r06,

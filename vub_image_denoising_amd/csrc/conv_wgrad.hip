@@ -16,9 +16,7 @@
 // pixel (k) index contiguous per lane, so bf16 fragments come out of LDS with
 // the gfx950 transpose read ds_read_b64_tr_b16 and fp32 fragments with one
 // ds_read_b32 per lane (v_mfma_f32_16x16x4_f32 takes one k per lane group).
-#include "rdn_common.h"
-
-#include <cstdlib>
+#include "rdn_launch.h"
 
 namespace {
 
@@ -303,11 +301,7 @@ static int auto_splits(const rdn_wgrad_desc* d) {
   const int64_t P = (int64_t)d->n * d->h * d->w;
   // ~2 blocks per CU (round 4, interleaved: 512 1771 / 1957, 256 1765 / 1939, 128 1767 /
   // 1941 img/s B16 / B32, profiles/r04_v31_wg2_blocks_ab.txt; RDN_WG2_BLOCKS for A/B)
-  static const int64_t target = [] {
-    const char* e = getenv("RDN_WG2_BLOCKS");
-    const int v = e ? atoi(e) : 0;
-    return (int64_t)(v > 0 ? v : 512);
-  }();
+  static const int64_t target = rdn_env_int("RDN_WG2_BLOCKS", 512);
   int64_t s = (target + tiles - 1) / tiles;
   const int64_t maxs = (P + 1023) / 1024;                 // >= 1024 pixels per split
   if (s > maxs) s = maxs;

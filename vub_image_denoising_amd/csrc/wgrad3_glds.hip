@@ -36,7 +36,7 @@
 // Pixels outside the image (partial tiles, halo borders) and channels past mdim
 // load 16 zero bytes from a device-side zero block, so stale stage bytes never
 // reach the MFMAs.
-#include "rdn_common.h"
+#include "rdn_device.h"
 
 
 #include <type_traits>
@@ -96,9 +96,6 @@ __device__ __forceinline__ int rot(int x) {
   else return 0;                                          // 32, 96, 160: conflict-free as is
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // DMAs wave w issues per tile: PA_ dY pieces + halo pieces w, w+4, ... < HPC;
 // wait until at most `ahead` later tiles of this wave's DMAs are in flight
 template <int PA_, int HPC, int NW, int K, int W = 0>
@@ -117,23 +114,9 @@ __device__ __forceinline__ void wait_own(int wave, int ahead) {
   else wait_own_k<PA_, HPC, NW, 2>(wave);
 }
 
-// One LDS-DMA wave-instruction: 16 B per lane from `src` to LDS byte dst + lane*16
-// (dst wave-uniform, in M0).  Inline asm, so that the compiler does not see an
-// LDS write pending on the VM counter: with the builtin it waits vmcnt(0) before
-// every ds_read of the array, which drains the ring (the counted waits above are
-// the only ordering, cdna_hip_programming.md §5, "Read a staged buffer one phase
-// AFTER the wait that retires it").
-__device__ __forceinline__ void glds16(const void* src, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(__builtin_amdgcn_readfirstlane(dst))
-               : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)p;
-}
-
+// (rdn_device.h, glds16: the counted waits above are the only ordering of the DMAs --
+// cdna_hip_programming.md §5, "Read a staged buffer one phase AFTER the wait that
+// retires it")
 template <int BM, int CK>
 __global__ __launch_bounds__((Geo<BM, CK>::NTH), 1) void wgrad3_glds_kernel(rdn_wgrad_desc d, int tiles_x, int tiles_y, int ntiles,
                                                              int tiles_per_block) {

@@ -19,9 +19,7 @@
 //
 // The dYpre tile of image pixels outside the image is zero, so partial tiles
 // contribute nothing.  Splits are summed by rdn_wgrad_reduce (fixed order).
-#include "rdn_common.h"
-
-#include <cstdlib>
+#include "rdn_launch.h"
 
 namespace {
 
@@ -583,11 +581,7 @@ Plan plan(const rdn_wgrad_desc* d) {
     // compute stream (gate-out, batched reduce): 192: 1767 / 1991, 160: 1777 / 1997,
     // 128: 1777 / 2011 img/s B16 / B32, then 128: 1764 / 1975, 112: 1759 / 1957,
     // 96: 1730 / 1927 (profiles/r04_v28_wglds_blocks_ab.txt, r04_v29_*).  RDN_WGLDS_BLOCKS
-    static const int gtarget = [] {
-      const char* e = getenv("RDN_WGLDS_BLOCKS");
-      const int v = e ? atoi(e) : 0;
-      return v > 0 ? v : 128;
-    }();
+    static const int gtarget = rdn_env_int("RDN_WGLDS_BLOCKS", 128);
     int s = d->splits > 0 ? d->splits : gtarget / base;
     const int maxs = (p.ntiles + 1) / 2;                             // >= 2 tiles per block
     if (s > maxs) s = maxs;

@@ -44,7 +44,7 @@ def main():
 
     rows = []
     for J in eng.layers:
-        K = J.extra.get("gates")
+        K = J.bwd.gates
         if K is None:
             continue
         d_go = J.dgrad_desc
@@ -56,7 +56,7 @@ def main():
         P = eng.P[olvl]
         pre = eng.bufs[K.pre]
         dd = eng._slice(K.ddst)
-        dyp, pws = K.extra["dyp"], K.extra["pws"]
+        dyp, pws = K.bwd.dyp, K.bwd.pws
         alpha = eng.named[K.act + ".weight"].data_ptr()
 
         def prelu():

@@ -182,3 +182,38 @@ def test_trainer_variants_keep_reference_signatures():
     # direct variant: forward = forward_diffusion + direct_sampling (diffusion_RDUnet_direct.py:203-206)
     assert D.DiffusionModel.forward is not A.DiffusionModel.forward
     assert issubclass(D.DiffusionModel, A.DiffusionModel)
+
+
+def test_conv_layer_extra_is_a_read_only_view_of_the_typed_state():
+    """``ConvLayer.extra`` (read by bench.py, tests and scripts) is built from the typed
+    fields: exactly the keys info / splitk / dense3 / dw / gates / side_slab, each
+    present only where the layer has that state, and it takes no writes."""
+    from vub_image_denoising_amd.engine import ConvLayer, LayerBwd, Slice
+
+    def layer(name):
+        return ConvLayer(name, name + ".actv", "c3", 0, 32, 32, 16, 16, Slice("X"), Slice("X", 32), "PRE_" + name)
+
+    fwd = layer("conv_0")            # forward-only engine, nothing planned yet
+    assert dict(fwd.extra) == {} and fwd.bwd is None
+    assert "dense3" not in fwd.extra and "splitk" not in fwd.extra and "dw" not in fwd.extra
+    assert fwd.extra.get("info", {}) == {} and fwd.extra.get("gates") is None
+    fwd.info = {"fwd": ("fwd", "conv_0", "some_kernel", 1234, 56)}
+    fwd.splitk, fwd.dense3, fwd.dense3_skip = 4, object(), True
+    assert set(fwd.extra) == {"info", "splitk", "dense3"}
+    assert fwd.extra["info"]["fwd"][3] == 1234 and fwd.extra["splitk"] == 4 and fwd.extra["dense3"] is fwd.dense3
+
+    side, fused = layer("conv_1"), layer("conv_2")   # train engine: side-stream layer, fused finisher
+    side.bwd = LayerBwd(1, 1, 4096, 0, [0, 1, 2], [0, 64, 128], side_slab=0, gated_by=fused)
+    fused.bwd = LayerBwd(0, 0, 8192, 0, [3, 4, 5], [192, 256, 320], dw=True, gates=side)
+    side.info = fused.info = {}
+    assert set(side.extra) == {"info", "dw", "side_slab"}    # (gated_by stays engine-internal)
+    assert side.extra["dw"] is False and side.extra["side_slab"] == 0
+    assert set(fused.extra) == {"info", "dw", "gates"}
+    assert fused.extra["dw"] is True and fused.extra["gates"] is side and "side_slab" not in fused.extra
+    for L in (fwd, side, fused):
+        with pytest.raises(TypeError):
+            L.extra["dw"] = True
+        with pytest.raises(TypeError):
+            del L.extra["info"]
+        with pytest.raises(AttributeError):
+            L.extra = {}

@@ -27,6 +27,8 @@ import os
 import warnings
 import weakref
 from dataclasses import dataclass, field
+from functools import partialmethod
+from types import MappingProxyType
 
 import torch
 
@@ -295,6 +297,40 @@ class Slice:
     c0: int = 0
 
 
+# who produces a layer's dYpre (the gradient at its PReLU input)
+GATE_LOADER = "loader"       # its own dgrad / wgrad loaders gate dY with the saved PReLU input
+GATE_FINISHER = "finisher"   # the dgrad epilogue of its last consumer (gate-out, `gated_by`)
+GATE_PRELU = "prelu"         # the separate rdn_prelu_bwd pass
+
+
+@dataclass
+class LayerBwd:
+    """Backward launch state of one layer in a train engine.  ``gate`` and ``dw`` are
+    the layer's path: who produces dYpre, and whether the gradients come from the
+    fused dgrad+wgrad kernel on the compute stream (``dw``; ``pregated``: it reads
+    dYpre, else it gates in its loader) or from dgrad there + wgrad on the side stream."""
+    bidx: int                 # position in backward order
+    slot: int                 # ring slot of its dYpre / partials / fused slabs (bidx % slots)
+    dyp: int                  # dYpre pointer (the slot's buffer)
+    olvl: int                 # level of the output grid
+    pidx: list                # parameter indices: weight, bias, PReLU weight
+    goff: list                # their byte offsets in a flat gradient buffer
+    gate: str = GATE_PRELU
+    dw: bool = False
+    pregated: bool = False
+    wgrad: tuple = ()         # (splits, mdim, ndim, ndim_real, taps) of the weight-gradient slabs
+    dw_bytes: int = 0         # fused kernel's slabs (0: not dw)
+    dw_cols: int = 0          # input channels per slab (< ndim: column parts)
+    part_bytes: int = 0       # dalpha / dbias partials
+    part_rows: int = 0        # partial rows the reduce sums besides the loaders' (0: GATE_LOADER)
+    pws: int = 0              # partials pointer (the slot's buffer)
+    side_slab: int | None = None   # side-stream layers: entry of the ws_side ring
+    gates: ConvLayer | None = field(default=None, repr=False)      # layer whose dYpre this dgrad epilogue writes
+    gated_by: ConvLayer | None = field(default=None, repr=False)   # ... and the reverse link
+    ev_ready: object = None   # dYpre ready (compute stream)
+    ev_done: object = None    # weight gradients reduced, slot free
+
+
 @dataclass
 class ConvLayer:
     name: str                 # module prefix, e.g. "block_0_0.conv_1"
@@ -316,10 +352,23 @@ class ConvLayer:
     fwd_desc: object = None
     dgrad_desc: object = None
     wgrad_desc: object = None
-    wgrad_splits: int = 0
     pack_fwd: tuple = ()
     pack_dgrad: tuple = ()
-    extra: dict = field(default_factory=dict)
+    # bound by the engine that runs the layer
+    splitk: int = 0             # forward runs split-K in this many slices (0: single pass)
+    dense3: object = None       # conv_0 of a fused dense block: the conv_0..2 launch's descriptor
+    dense3_skip: bool = False   # conv_1 / conv_2 of such a block: no launch of their own
+    info: dict | None = None    # launch name -> (phase, layer, key, flops, bytes[, fused_min]) for the tracer
+    bwd: LayerBwd | None = None  # backward launch state (None in forward-only engines)
+
+    @property
+    def extra(self):
+        """Read-only view of the bound state for tests, bench.py and scripts; a key is
+        present only where the layer has that state."""
+        S = self.bwd
+        v = {"info": self.info, "splitk": self.splitk or None, "dense3": self.dense3, "dw": S and S.dw,
+             "gates": S and S.gates, "side_slab": S and S.side_slab}
+        return MappingProxyType({k: x for k, x in v.items() if x is not None})
 
 
 @dataclass
@@ -566,7 +615,8 @@ def weight_packs(module, fp, layers, dtype) -> WeightPacks:
 
 # ----------------------------------------------------------------- engine
 # descriptor pointers that select a kernel variant (kept as they are by the probes)
-_CONV_SELECT = ("gate", "gate_alpha", "gout", "gout_pre", "gout_alpha", "gout_part")
+_SELECT = {H.ConvDesc: ("gate", "gate_alpha", "gout", "gout_pre", "gout_alpha", "gout_part"),
+           H.WgradDesc: ("a_gate", "a_gate_alpha", "part")}
 
 
 class UNetEngine:
@@ -760,7 +810,7 @@ class UNetEngine:
         for L in self.layers:
             s = lib.rdn_conv_fwd_splits(C.byref(L.fwd_desc))
             if s > 0:
-                L.extra["splitk"] = s
+                L.splitk = s
                 need = max(need, lib.rdn_conv_fwd_splitk_workspace_size(C.byref(L.fwd_desc), s))
         if need:
             self.ws_fwd = torch.empty(need // 4 + 4, dtype=torch.float32, device=self.device)
@@ -809,152 +859,140 @@ class UNetEngine:
                 d.wp[k], d.kp[k] = packed.data_ptr(), packed.shape[1]
                 d.bias[k] = self.named[L.name + ".bias"].data_ptr()
                 d.alpha[k] = self.named[L.act + ".weight"].data_ptr()
-            L0.extra["dense3"] = d
+            L0.dense3 = d
             for L in Ls[1:]:
-                L.extra["dense3_skip"] = True
+                L.dense3_skip = True
+
+    def _gate_operands(self, L):
+        """(pointer, pixel stride, alpha pointer) of the saved PReLU input that gates dY."""
+        pre = self.bufs[L.pre]
+        return pre.data_ptr(), pre.shape[1], self.named[L.act + ".weight"].data_ptr()
+
+    def _dgrad_desc(self, L, gated):
+        """Input gradient as a forward-shaped conv over dYpre (``gated``: over dY,
+        gated by the saved PReLU input in the loader)."""
+        d = H.ConvDesc(dtype=self.code)
+        packed = L.pack_dgrad[8]
+        d.wp, d.kp = packed.data_ptr(), packed.shape[1]
+        d.x, d.x_c0 = L.bwd.dyp, 0
+        n, h, w = self.grid[L.level]
+        flags = 0
+        if L.kind == "c3":
+            d.gather, d.hin, d.win = H.RDN_G_CONV3, h, w
+            d.x_ps, d.cin = L.cout_pad, L.cout_pad
+            d.ncols = d.cout = L.cin
+            if gated:
+                d.x, d.x_ps, d.x_c0, d.x_pl = self._slice(L.ddst)
+                d.gate, d.gate_ps, d.gate_alpha = self._gate_operands(L)
+        elif L.kind == "down":       # per-pixel GEMM on the low-res grid, scattered to 2x2
+            d.gather, d.hin, d.win = H.RDN_G_PIX, h, w
+            d.x_ps, d.cin = L.cout, L.cout
+            d.ncols, d.cout = 4 * L.cin, L.cin
+            flags |= H.EPI_SCATTER2
+        else:                        # conv-s2 gather of the hi-res dYpre
+            d.gather, d.hin, d.win = H.RDN_G_S2, 2 * h, 2 * w
+            d.x_ps, d.cin = L.cout, L.cout
+            d.ncols = d.cout = L.cin
+        d.n, d.h, d.w = n, h, w
+        d.out, d.out_ps, d.out_c0, d.out_pl = self._slice(L.dsrc)
+        if L.accum:
+            flags |= H.EPI_ACCUM
+        if L.resid is not None:      # d(x) += dOut through "out_3 + x" (Unet_model.py:89)
+            flags |= H.EPI_RESID
+            d.res, d.res_ps, d.res_c0, d.res_pl = self._slice(L.ddst)
+            d.res_climit = L.resid_c
+        d.flags = flags
+        return d
+
+    def _wgrad_desc(self, L, gated):
+        """Weight gradient dYpre^T x (gathered input); ``splits`` left 0 (automatic)."""
+        n, h, w = self.grid[L.level]
+        wg = H.WgradDesc(dtype=self.code, n=n, h=h, w=w)
+        dyp = L.bwd.dyp
+        if L.kind == "c3":
+            wg.gather, wg.hin, wg.win = H.RDN_G_CONV3, h, w
+            wg.a, wg.a_ps, wg.a_c0, wg.mdim = dyp, L.cout_pad, 0, L.cout
+            wg.b, wg.b_ps, wg.b_c0, wg.b_pl = self._slice(L.src)
+            wg.ndim = L.cin_pad
+            if gated:
+                wg.a, wg.a_ps, wg.a_c0, wg.a_pl = self._slice(L.ddst)
+                wg.a_gate, wg.a_gate_ps, wg.a_gate_alpha = self._gate_operands(L)
+        elif L.kind == "down":
+            wg.gather, wg.hin, wg.win = H.RDN_G_S2, 2 * h, 2 * w
+            wg.a, wg.a_ps, wg.a_c0, wg.mdim = dyp, L.cout, 0, L.cout
+            wg.b, wg.b_ps, wg.b_c0, wg.b_pl = self._slice(L.src)
+            wg.ndim = L.cin
+        else:
+            wg.gather, wg.hin, wg.win = H.RDN_G_S2, 2 * h, 2 * w
+            wg.a, wg.a_ps, wg.a_c0, wg.a_pl = self._slice(L.src)
+            wg.mdim = L.cin
+            wg.b, wg.b_ps, wg.b_c0, wg.ndim = dyp, L.cout, 0, L.cout
+        return wg
+
+    def _plan_path(self, L):
+        """A layer's backward path: (gated in the loaders, split count of the fused
+        dgrad+wgrad kernel or 0, dgrad and wgrad descriptors).  In priority order: the
+        pre-gated fused kernel (multi-chunk layers), the fused kernel gating in its own
+        loader (also multi-chunk: column parts), the separate kernels gating in their
+        loaders when the weight gradient reads the gated operand in ONE input-channel
+        chunk, else the separate kernels over dYpre (always: NCHW dy, the 2x2 convs)."""
+        lib = H.lib()
+        gate_ok = L.kind == "c3" and L.ddst is not None and FUSE_PRELU
+        single = False
+        if gate_ok:
+            n, h, w = self.grid[L.level]
+            probe = H.WgradDesc(dtype=self.code, gather=H.RDN_G_CONV3, n=n, h=h, w=w, hin=h, win=w,
+                                mdim=L.cout, ndim=L.cin_pad)
+            single = lib.rdn_wgrad_chunks(C.byref(probe)) == 1
+        dw_ok = gate_ok and FUSE_DW and L.src.buf not in self.pure_inputs
+        fused_kernel = [False, True] if not single and DW_PREGATED else [True]
+        for gated in fused_kernel if dw_ok else []:
+            d, wg = self._dgrad_desc(L, gated), self._wgrad_desc(L, gated)
+            dw = lib.rdn_conv_dgrad_wgrad_splits(C.byref(d), C.byref(wg))
+            if dw > 0:
+                return gated, dw, d, wg
+        return single, 0, self._dgrad_desc(L, single), self._wgrad_desc(L, single)
 
     def _build_bwd(self):
         lib = H.lib()
         ws_need = 0
         for b, L in enumerate(reversed(self.layers)):   # backward order -> ring slot
-            L.extra["slot"] = b % self.slots
-            L.extra["bidx"] = b
-            L.extra["dyp"] = self.dyp[L.extra["slot"]].data_ptr()
-        for L in self.layers:
-            olvl = self._out_level(L)
-            dyp = L.extra["dyp"]
-            # 3x3 convs whose output gradient arrives as an NHWC slice run the
-            # PReLU backward inside their dgrad / wgrad loaders (gate = saved
-            # PReLU input); the output conv (NCHW dy) and the 2x2 convs keep
-            # the separate rdn_prelu_bwd pass producing dYpre.
-            gate_ok = (L.kind == "c3" and L.ddst is not None) and FUSE_PRELU
-            fused = gate_ok
-            if fused:  # only when the wgrad reads operand A (with the gate) in one chunk
-                n_, h_, w_ = self.grid[L.level]
-                probe = H.WgradDesc(dtype=self.code, gather=H.RDN_G_CONV3, n=n_, h=h_, w=w_, hin=h_, win=w_,
-                                    mdim=L.cout, ndim=L.cin_pad)
-                fused = lib.rdn_wgrad_chunks(C.byref(probe)) == 1
-            pre = self.bufs[L.pre]
-            alpha = self.named[L.act + ".weight"]
-            pure = L.src.buf in self.pure_inputs
-
-            def build(fused):
-                # --- input gradient (dgrad) as a forward-shaped conv over dYpre
-                d = H.ConvDesc()
-                d.dtype = self.code
-                packed = L.pack_dgrad[8]
-                d.wp, d.kp = packed.data_ptr(), packed.shape[1]
-                d.x, d.x_c0 = dyp, 0
-                flags = 0
-                if L.kind == "c3":
-                    n, h, w = self.grid[L.level]
-                    d.gather, d.hin, d.win = H.RDN_G_CONV3, h, w
-                    d.x_ps, d.cin = L.cout_pad, L.cout_pad
-                    d.ncols = d.cout = L.cin
-                    if fused:
-                        d.x, d.x_ps, d.x_c0, d.x_pl = self._slice(L.ddst)
-                        d.gate, d.gate_ps, d.gate_alpha = pre.data_ptr(), pre.shape[1], alpha.data_ptr()
-                elif L.kind == "down":       # per-pixel GEMM on the low-res grid, scattered to 2x2
-                    n, h, w = self.grid[L.level]
-                    d.gather, d.hin, d.win = H.RDN_G_PIX, h, w
-                    d.x_ps, d.cin = L.cout, L.cout
-                    d.ncols, d.cout = 4 * L.cin, L.cin
-                    flags |= H.EPI_SCATTER2
-                else:                        # conv-s2 gather of the hi-res dYpre
-                    n, h, w = self.grid[L.level]
-                    d.gather, d.hin, d.win = H.RDN_G_S2, 2 * h, 2 * w
-                    d.x_ps, d.cin = L.cout, L.cout
-                    d.ncols = d.cout = L.cin
-                d.n, d.h, d.w = n, h, w
-                d.out, d.out_ps, d.out_c0, d.out_pl = self._slice(L.dsrc)
-                if L.accum:
-                    flags |= H.EPI_ACCUM
-                if L.resid is not None:      # d(x) += dOut through "out_3 + x" (Unet_model.py:89)
-                    flags |= H.EPI_RESID
-                    d.res, d.res_ps, d.res_c0, d.res_pl = self._slice(L.ddst)
-                    d.res_climit = L.resid_c
-                d.flags = flags
-                # --- weight gradient
-                wg = H.WgradDesc()
-                wg.dtype = self.code
-                if L.kind == "c3":
-                    n, h, w = self.grid[L.level]
-                    wg.gather, wg.n, wg.h, wg.w, wg.hin, wg.win = H.RDN_G_CONV3, n, h, w, h, w
-                    wg.a, wg.a_ps, wg.a_c0, wg.mdim = dyp, L.cout_pad, 0, L.cout
-                    wg.b, wg.b_ps, wg.b_c0, wg.b_pl = self._slice(L.src)
-                    wg.ndim = L.cin_pad
-                    taps, ndim_real = 9, L.cin
-                    if fused:
-                        wg.a, wg.a_ps, wg.a_c0, wg.a_pl = self._slice(L.ddst)
-                        wg.a_gate, wg.a_gate_ps, wg.a_gate_alpha = pre.data_ptr(), pre.shape[1], alpha.data_ptr()
-                elif L.kind == "down":
-                    n, h, w = self.grid[L.level]
-                    wg.gather, wg.n, wg.h, wg.w, wg.hin, wg.win = H.RDN_G_S2, n, h, w, 2 * h, 2 * w
-                    wg.a, wg.a_ps, wg.a_c0, wg.mdim = dyp, L.cout, 0, L.cout
-                    wg.b, wg.b_ps, wg.b_c0, wg.b_pl = self._slice(L.src)
-                    wg.ndim = L.cin
-                    taps, ndim_real = 4, L.cin
-                else:
-                    n, h, w = self.grid[L.level]
-                    wg.gather, wg.n, wg.h, wg.w, wg.hin, wg.win = H.RDN_G_S2, n, h, w, 2 * h, 2 * w
-                    wg.a, wg.a_ps, wg.a_c0, wg.a_pl = self._slice(L.src)
-                    wg.mdim = L.cin
-                    wg.b, wg.b_ps, wg.b_c0, wg.ndim = dyp, L.cout, 0, L.cout
-                    taps, ndim_real = 4, L.cout
-                return d, wg, taps, ndim_real
-
-            d, wg, taps, ndim_real = build(fused)
-            dw = 0
-            pregated = False
-            if gate_ok and FUSE_DW and not pure and not fused and DW_PREGATED:
-                # the pre-gated fused kernel (dYpre from the PReLU pass / a gate-out finisher)
-                pregated = lib.rdn_conv_dgrad_wgrad_splits(C.byref(d), C.byref(wg)) > 0
-            if gate_ok and FUSE_DW and not pure and not pregated:
-                # the fused dgrad + wgrad kernel gates in its own loader, also for the
-                # multi-chunk level-1 convs (column halves, rdn_conv_dgrad_wgrad_cols)
-                dg, wgg, _, _ = (d, wg, taps, ndim_real) if fused else build(True)
-                wgg.splits = 0
-                wgg.splits = lib.rdn_wgrad_splits(C.byref(wgg))
-                dw = lib.rdn_conv_dgrad_wgrad_splits(C.byref(dg), C.byref(wgg))
-                if dw > 0 and not fused:
-                    fused, d, wg = True, dg, wgg
-            L.extra["fused"] = fused
-            L.dgrad_desc = d
-            wg.splits = 0
-            splits = lib.rdn_wgrad_splits(C.byref(wg))
-            wg.splits = splits
-            dw = 0
-            if (fused or pregated) and FUSE_DW and L.src.buf not in self.pure_inputs:
-                dw = lib.rdn_conv_dgrad_wgrad_splits(C.byref(d), C.byref(wg))
-            L.extra["dw"] = dw > 0
-            L.extra["dw_bytes"] = 0
-            L.extra["dw_cols"] = wg.ndim
+            olvl, slot = self._out_level(L), b % self.slots
+            pidx = [self.fp.index[n] for n in (L.name + ".weight", L.name + ".bias", L.act + ".weight")]
+            L.bwd = S = LayerBwd(b, slot, self.dyp[slot].data_ptr(), olvl, pidx, [4 * self.fp.offsets[i] for i in pidx])
+            fused, dw, d, wg = self._plan_path(L)
+            S.gate, S.dw, S.pregated = GATE_LOADER if fused else GATE_PRELU, dw > 0, dw > 0 and not fused
+            L.dgrad_desc, L.wgrad_desc = d, wg
+            S.dw_cols = wg.ndim
             if dw > 0:   # the fused kernel's slabs: one per block of its persistent grid
-                splits = wg.splits = dw
-                L.extra["dw_bytes"] = dw * wg.mdim * 9 * wg.ndim * 4
-                L.extra["dw_cols"] = lib.rdn_conv_dgrad_wgrad_cols(C.byref(d), C.byref(wg))
+                wg.splits = dw
+                S.dw_bytes = dw * wg.mdim * 9 * wg.ndim * 4
+                S.dw_cols = lib.rdn_conv_dgrad_wgrad_cols(C.byref(d), C.byref(wg))
             else:
+                wg.splits = lib.rdn_wgrad_splits(C.byref(wg))
                 ws_need = max(ws_need, lib.rdn_wgrad_workspace_size(C.byref(wg)))
             # dalpha / dbias partials: the fused loaders' per-split rows, else the
             # separate PReLU-backward pass's per-block rows
-            L.extra["part_bytes"] = (splits * 2 * wg.mdim * 4 if fused else
-                                     lib.rdn_prelu_bwd_workspace_size(self.code, self.P[olvl], L.cout, L.cout_pad))
-            L.wgrad_desc = wg
-            L.extra["wgrad"] = (splits, wg.mdim, wg.ndim, ndim_real, taps)
-            pidx = [self.fp.index[n] for n in (L.name + ".weight", L.name + ".bias", L.act + ".weight")]
-            L.extra["pidx"] = pidx
-            L.extra["goff"] = [4 * self.fp.offsets[i] for i in pidx]   # byte offsets in a flat gradient buffer
-            L.extra["olvl"] = olvl
+            if fused:
+                S.part_bytes = wg.splits * 2 * wg.mdim * 4
+            else:
+                S.part_rows = lib.rdn_prelu_bwd_blocks(self.code, self.P[olvl], L.cout_pad)
+                S.part_bytes = lib.rdn_prelu_bwd_workspace_size(self.code, self.P[olvl], L.cout, L.cout_pad)
+            S.wgrad = (wg.splits, wg.mdim, wg.ndim, L.cout if L.kind == "up" else L.cin, 9 if L.kind == "c3" else 4)
         self._plan_gate_out()
+        self._bind_bwd_buffers(ws_need)
+
+    def _bind_bwd_buffers(self, ws_need):
+        """Sizes the pool's shared workspaces from the planned layers and binds each
+        layer's slab / partials pointers and events."""
         self.ws = self._shared("ws", lambda: torch.zeros(max(ws_need // 4, 4), dtype=torch.float32,
                                                           device=self.device))
         # per slot: fused layers' slabs (written from the compute stream while the side
         # stream may still reduce an earlier layer's) and the dalpha/dbias partials
         dwb, pwb = [0] * self.slots, [16] * self.slots
-        for L in self.layers:
-            sl = L.extra["slot"]
-            dwb[sl] = max(dwb[sl], L.extra["dw_bytes"])
-            pwb[sl] = max(pwb[sl], L.extra["part_bytes"])
+        for S in (L.bwd for L in self.layers):
+            dwb[S.slot] = max(dwb[S.slot], S.dw_bytes)
+            pwb[S.slot] = max(pwb[S.slot], S.part_bytes)
         f32 = dict(dtype=torch.float32, device=self.device)
         self.ws_dw = [self._shared(("ws_dw", i), lambda n=n: torch.zeros((n // 4 + 3) // 4 * 4, **f32)) if n else None
                       for i, n in enumerate(dwb)]
@@ -967,23 +1005,21 @@ class UNetEngine:
                                     for i in range(1, self.side_batch)]
         k = 0
         for L in reversed(self.layers):
-            if not L.extra["dw"]:
-                L.extra["side_slab"] = k % self.side_batch
+            S, wg = L.bwd, L.wgrad_desc
+            S.pws = self.pws[S.slot].data_ptr()
+            if S.dw:
+                wg.ws = self.ws_dw[S.slot].data_ptr()
+            else:
+                S.side_slab = k % self.side_batch
+                wg.ws = self.ws_side[S.side_slab].data_ptr()
                 k += 1
-        for L in self.layers:
-            L.extra["pws"] = self.pws[L.extra["slot"]].data_ptr()
-            L.wgrad_desc.ws = (self.ws_dw[L.extra["slot"]].data_ptr() if L.extra["dw"]
-                               else self.ws_side[L.extra["side_slab"]].data_ptr())
-            if L.extra["fused"]:
-                L.wgrad_desc.part = L.extra["pws"]
-        for L in self.layers:   # the finisher's epilogue writes the gated layer's partials
-            K = L.extra.get("gates")
-            if K is not None:
-                L.dgrad_desc.gout_part = K.extra["pws"]
+            if S.gate == GATE_LOADER:
+                wg.part = S.pws
+            if S.gated_by is not None:   # the finisher's epilogue writes this layer's partials
+                S.gated_by.dgrad_desc.gout_part = S.pws
         if self.side is not None:   # per layer: dYpre ready (compute stream) / slot free (side stream)
             for L in self.layers:
-                L.extra["ev_ready"] = torch.cuda.Event()
-                L.extra["ev_done"] = torch.cuda.Event()
+                L.bwd.ev_ready, L.bwd.ev_done = torch.cuda.Event(), torch.cuda.Event()
             self.ev_begin = torch.cuda.Event()
             self.ev_end = torch.cuda.Event()
 
@@ -1000,7 +1036,7 @@ class UNetEngine:
         lib = H.lib()
         index = {id(L): i for i, L in enumerate(self.layers)}
         for K in self.layers:
-            if K.extra["fused"] or K.dst is None or K.kind == "down" or K.cout != K.cout_pad:
+            if K.bwd.gate == GATE_LOADER or K.dst is None or K.kind == "down" or K.cout != K.cout_pad:
                 continue
             lo, hi = K.dst.c0, K.dst.c0 + K.cout
             cons = [L for L in self.layers if index[id(L)] > index[id(K)] and L.src.buf == K.dst.buf
@@ -1008,7 +1044,7 @@ class UNetEngine:
             if not cons:
                 continue
             J = min(cons, key=lambda L: index[id(L)])   # last in backward order
-            dwj = bool(J.extra["dw"])
+            dwj = J.bwd.dw
             # a residual reader of the slice adds its gradient in its own dgrad epilogue;
             # the fused dgrad+wgrad finisher runs after every such reader in backward
             # order (the next block's conv_3 before its conv_0), the others never do
@@ -1021,12 +1057,12 @@ class UNetEngine:
             # per step; the fused dgrad+wgrad finisher prefetches it with the dX operand)
             if self._out_level(K) == 0 and not dwj:
                 continue
-            if (J.kind != "c3" or J.extra.get("gates") is not None or J.src.buf in self.pure_inputs
+            if (J.kind != "c3" or J.bwd.gates is not None or J.src.buf in self.pure_inputs
                     or J.cin != J.cin_pad or J.src.c0 + J.cin != hi or J.src.c0 > lo):
                 continue
             pre = self.bufs[K.pre]
             d = J.dgrad_desc
-            d.gout, d.gout_ps = K.extra["dyp"], K.cout_pad
+            d.gout, d.gout_ps = K.bwd.dyp, K.cout_pad
             d.gout_pre, d.gout_pre_ps = pre.data_ptr(), pre.shape[1]
             d.gout_alpha = self.named[K.act + ".weight"].data_ptr()
             d.gout_part = 4096   # stand-in until the workspace exists (rows probe)
@@ -1034,7 +1070,7 @@ class UNetEngine:
             if dwj:   # one partial row per block of the fused kernel's persistent grid
                 if K.resid is not None:   # K's own dgrad reads its dY again (residual operand)
                     d.flags |= H.EPI_GOUT_KEEP
-                wq = self._probe_copy(J.wgrad_desc, H.WgradDesc, ("a_gate", "a_gate_alpha"))   # (part: stand-in)
+                wq = self._probe_copy(J.wgrad_desc, keep=("a_gate", "a_gate_alpha"))   # (part: stand-in)
                 rows = lib.rdn_conv_dgrad_wgrad_gate_rows(C.byref(d), C.byref(wq)) if GATE_OUT_DW else 0
             else:
                 rows = lib.rdn_conv_gate_rows(C.byref(d))
@@ -1043,50 +1079,35 @@ class UNetEngine:
                 d.gout = d.gout_pre = d.gout_alpha = d.gout_part = None
                 d.gout_ps = d.gout_pre_ps = d.gout_c0 = 0
                 continue
-            J.extra["gates"] = K
-            K.extra["gated_by"] = J
-            K.extra["part_rows"] = rows
-            K.extra["part_bytes"] = max(K.extra["part_bytes"], rows * 2 * K.cout * 4)
+            J.bwd.gates, K.bwd.gated_by, K.bwd.gate = K, J, GATE_FINISHER
+            K.bwd.part_rows = rows
+            K.bwd.part_bytes = max(K.bwd.part_bytes, rows * 2 * K.cout * 4)
 
     @staticmethod
-    def _probe_copy(desc, cls, keep):
+    def _probe_copy(desc, keep=None):
         """Copy of a descriptor whose per-call pointers (bound at launch time) are
         stand-ins, for the dispatch probe; pointers that select a kernel variant
-        (`keep`) stay as they are."""
+        (`keep`, default: the descriptor type's) stay as they are."""
+        cls = type(desc)
+        keep = _SELECT[cls] if keep is None else keep
         d = cls.from_buffer_copy(desc)
         for name, typ in cls._fields_:
             if name not in keep and issubclass(typ, (C.c_void_p, C._Pointer)) and not getattr(d, name):
                 setattr(d, name, C.cast(C.c_void_p(4096), typ) if typ is not C.c_void_p else 4096)
         return d
 
-    def _kernel_key(self, desc):
-        """Name of the kernel instantiation a conv descriptor launches, as the
-        library's own dispatch decides it (rdn_conv_kernel_name)."""
-        d = self._probe_copy(desc, H.ConvDesc, _CONV_SELECT)
+    def _probe_key(self, probe, *descs):
+        """Name of the kernel instantiation the library's own dispatch picks for the
+        descriptor(s): ``probe`` is one of its rdn_*_kernel_name functions."""
+        args = [C.byref(self._probe_copy(d) if type(d) in _SELECT else d) for d in descs]
         buf = C.create_string_buffer(128)
-        H.check(H.lib().rdn_conv_kernel_name(C.byref(d), buf, 128), "rdn_conv_kernel_name")
+        H.check(getattr(H.lib(), probe)(*args, buf, 128), probe)
         return buf.value.decode()
 
-    def _wgrad_key(self, wg):
-        d = self._probe_copy(wg, H.WgradDesc, ("a_gate", "a_gate_alpha", "part"))
-        buf = C.create_string_buffer(128)
-        H.check(H.lib().rdn_wgrad_kernel_name(C.byref(d), buf, 128), "rdn_wgrad_kernel_name")
-        return buf.value.decode()
-
-    @staticmethod
-    def _dense3_key(d3):
-        """Kernel instantiation (tile geometry) the fused conv_0..2 launch takes."""
-        buf = C.create_string_buffer(128)
-        H.check(H.lib().rdn_dense3_kernel_name(C.byref(d3), buf, 128), "rdn_dense3_kernel_name")
-        return buf.value.decode()
-
-    def _dw_key(self, d, wg):
-        dc = self._probe_copy(d, H.ConvDesc, _CONV_SELECT)
-        wc = self._probe_copy(wg, H.WgradDesc, ("a_gate", "a_gate_alpha", "part"))
-        buf = C.create_string_buffer(128)
-        H.check(H.lib().rdn_conv_dgrad_wgrad_kernel_name(C.byref(dc), C.byref(wc), buf, 128),
-                "rdn_conv_dgrad_wgrad_kernel_name")
-        return buf.value.decode()
+    _kernel_key = partialmethod(_probe_key, "rdn_conv_kernel_name")
+    _wgrad_key = partialmethod(_probe_key, "rdn_wgrad_kernel_name")
+    _dense3_key = partialmethod(_probe_key, "rdn_dense3_kernel_name")   # (its pointers are bound at build time)
+    _dw_key = partialmethod(_probe_key, "rdn_conv_dgrad_wgrad_kernel_name")   # (dgrad, wgrad)
 
     def _build_info(self):
         """Per launch: kernel instantiation key + algorithmic FLOPs and bytes
@@ -1102,46 +1123,60 @@ class UNetEngine:
                 macs = Pout * L.cout * taps * L.cin
             fwd_bytes = es * (Pin * L.cin + Pout * L.cout * (2 if self.train else 1) +
                               (Pout * L.cout if L.resid is not None else 0))
-            fkey = self._kernel_key(L.fwd_desc) + (f",splitk{L.extra['splitk']}" if "splitk" in L.extra else "")
+            fkey = self._kernel_key(L.fwd_desc) + (f",splitk{L.splitk}" if L.splitk else "")
             info = {"fwd": ("fwd", L.name, fkey, 2 * macs, fwd_bytes)}
-            if "dense3" in L.extra:   # conv_0..2 in one launch: their algorithmic work summed below
+            if L.dense3 is not None:   # conv_0..2 in one launch: their algorithmic work summed below
                 info["dense3"] = None
-            if self.train:
+            S = L.bwd
+            if S is not None:
                 # a fused PReLU backward (gate in the loader) also reads the saved
                 # PReLU input of the output slice
-                gate = Pout * L.cout if L.extra.get("fused") else 0
-                gout = Pin * L.extra["gates"].cout if L.extra.get("gates") is not None else 0
+                gate = Pout * L.cout if S.gate == GATE_LOADER else 0
+                gout = Pin * S.gates.cout if S.gates is not None else 0
                 if L.dgrad_desc.flags & H.EPI_GOUT_KEEP:   # (dY stored beside its dYpre)
                     gout *= 2
                 dg_bytes = es * (Pout * L.cout + gate + Pin * L.cin * (2 if L.accum else 1) + gout +
                                  (Pin * L.resid_c if L.resid is not None else 0))
                 # (a fused layer's dgrad descriptor is the fused kernel's: no separate key)
-                dkey = "conv3_dw_kernel" if L.extra.get("dw") else self._kernel_key(L.dgrad_desc)
+                dkey = "conv3_dw_kernel" if S.dw else self._kernel_key(L.dgrad_desc)
                 info["dgrad"] = ("dgrad", L.name, dkey, 2 * macs, dg_bytes)
                 info["wgrad"] = ("wgrad", L.name, self._wgrad_key(L.wgrad_desc), 2 * macs,
                                  es * (Pout * L.cout + gate + Pin * L.cin))
-                if not (L.extra.get("fused") or "gated_by" in L.extra):
+                if S.gate == GATE_PRELU:
                     # the separate PReLU-backward pass: dY + PReLU input read, dYpre written
                     info["prelu"] = ("prelu", L.name, "prelu_bwd_kernel", 0, 3 * es * Pout * L.cout)
-                if L.extra.get("dw"):   # one pass: dY + gate + X read once, dX written
+                if S.dw:   # one pass: dY + gate + X read once, dX written
                     info["dw"] = ("dwgrad", L.name, self._dw_key(L.dgrad_desc, L.wgrad_desc), 4 * macs,
                                   dg_bytes + es * Pin * L.cin)
-            L.extra["info"] = info
+            L.info = info
         # the fused conv_0..2 launch: the three convs' algorithmic FLOPs and bytes (each
         # conv's input read once, output + PReLU input written once), as unfused
         by_name = {L.name: L for L in self.layers}
         for L in self.layers:
-            if "dense3" in L.extra:
+            if L.dense3 is not None:
                 blk = L.name[:-len(".conv_0")]
-                parts = [by_name[f"{blk}.conv_{k}"].extra["info"]["fwd"] for k in range(3)]
+                parts = [by_name[f"{blk}.conv_{k}"].info["fwd"] for k in range(3)]
                 # 6th entry: the fused launch's own minimal bytes (x read once, each
                 # conv's output and PReLU input written once: 32 + 3 x 32 channels)
                 Ls = [by_name[f"{blk}.conv_{k}"] for k in range(3)]
                 fused_min = es * self.P[L.level] * (Ls[0].cin + sum(2 * x.cout for x in Ls))
-                L.extra["info"]["dense3"] = ("fwd", f"{blk}.conv_0-2", self._dense3_key(L.extra["dense3"]),
-                                             sum(p[3] for p in parts), sum(p[4] for p in parts), fused_min)
+                L.info["dense3"] = ("fwd", f"{blk}.conv_0-2", self._dense3_key(L.dense3),
+                                    sum(p[3] for p in parts), sum(p[4] for p in parts), fused_min)
 
     # ------------------------------------------------------------------
+    @staticmethod
+    def _launch(info, what, L, fn, *args, on=()):
+        """One library launch of layer ``L`` between TRACER.start(info, *on) (``on``: the
+        stream, where it is not the current one) and .stop; a non-zero return code
+        raises as ``what[layer]``."""
+        tr = TRACER
+        tok = tr.start(info, *on) if tr is not None else None
+        rc = fn(*args)
+        if tok is not None:
+            tr.stop(tok)
+        if rc:
+            H.check(rc, f"{what}[{L.name}]")
+
     def forward(self, xs, t: torch.Tensor | None = None) -> torch.Tensor:
         """``xs``: the Program's NCHW fp32 inputs (contiguous, on the device)."""
         lib, st = H.lib(), H.stream_ptr()
@@ -1177,24 +1212,17 @@ class UNetEngine:
         last = self.layers[-1].fwd_desc
         last.out_nchw = y.data_ptr()
         last.res_nchw = x0.data_ptr() if prog.resid_input else None
-        fwd = lib.rdn_conv_fwd
-        tr = TRACER
+        launch = self._launch
         for L in self.layers:
-            if "dense3_skip" in L.extra:
+            if L.dense3_skip:
                 continue
-            d3 = L.extra.get("dense3")
-            tok = tr.start(L.extra["info"]["dense3" if d3 is not None else "fwd"]) if tr is not None else None
-            sk = L.extra.get("splitk")
-            if d3 is not None:
-                rc = lib.rdn_dense3_fwd(C.byref(d3), st)
-            elif sk:
-                rc = lib.rdn_conv_fwd_splitk(C.byref(L.fwd_desc), sk, self.ws_fwd.data_ptr(), st)
+            if L.dense3 is not None:
+                launch(L.info["dense3"], "conv_fwd", L, lib.rdn_dense3_fwd, C.byref(L.dense3), st)
+            elif L.splitk:
+                launch(L.info["fwd"], "conv_fwd", L, lib.rdn_conv_fwd_splitk, C.byref(L.fwd_desc), L.splitk,
+                       self.ws_fwd.data_ptr(), st)
             else:
-                rc = fwd(C.byref(L.fwd_desc), st)
-            if tok is not None:
-                tr.stop(tok)
-            if rc:
-                H.check(rc, f"conv_fwd[{L.name}]")
+                launch(L.info["fwd"], "conv_fwd", L, lib.rdn_conv_fwd, C.byref(L.fwd_desc), st)
         return y
 
     def backward(self, dy: torch.Tensor, need_dx):
@@ -1229,7 +1257,7 @@ class UNetEngine:
             side.wait_event(self.ev_begin)   # gradient buffer zeroed
         else:
             sst = st
-        tr = TRACER
+        launch = self._launch
         rev = list(reversed(self.layers))
         pending = []   # fused layers whose split-K reduces wait for one batched launch
         spending = []  # weight-gradient-stream layers whose reduces wait for one batched launch
@@ -1241,9 +1269,9 @@ class UNetEngine:
             jl = [j for _, j in spending]
             H.check(lib.rdn_wgrad_reduce_batch((H.ReduceJob * len(jl))(*jl), len(jl), sst), "wgrad_reduce_batch(side)")
             for Lp, _ in spending:
-                Lp.extra["ev_done"].record(side)
+                Lp.bwd.ev_done.record(side)
                 if sync is not None:
-                    sync.params_done(Lp.extra["pidx"], stream=side)
+                    sync.params_done(Lp.bwd.pidx, stream=side)
             spending.clear()
 
         def flush():
@@ -1255,9 +1283,9 @@ class UNetEngine:
                 H.check(lib.rdn_wgrad_reduce_batch((H.ReduceJob * n_)(*jl[i:i + n_]), n_, st), "wgrad_reduce_batch")
             for Lp, _ in pending:
                 if side is not None:
-                    Lp.extra["ev_done"].record(main)
+                    Lp.bwd.ev_done.record(main)
                 if sync is not None:
-                    sync.params_done(Lp.extra["pidx"], stream=None if side is None else main)
+                    sync.params_done(Lp.bwd.pidx, stream=None if side is None else main)
             pending.clear()
 
         def wait_done(Lw):
@@ -1268,109 +1296,77 @@ class UNetEngine:
                 flush()
             if any(Lp is Lw for Lp, _ in spending):
                 flush_side()
-            main.wait_event(Lw.extra["ev_done"])
+            main.wait_event(Lw.bwd.ev_done)
+
+        def wait_slot(bi):
+            """Before the compute stream writes the ring slot of backward index ``bi``:
+            wait for the layer that used the slot before (none in the first round)."""
+            if side is not None and bi >= self.slots:
+                wait_done(rev[bi - self.slots])
 
         for b, L in enumerate(rev):
-            if pending and not L.extra["dw"]:
+            S, info = L.bwd, L.info
+            dw, fused = S.dw, S.gate == GATE_LOADER
+            if pending and not dw:
                 flush()
-            info = L.extra["info"]
-            olvl = L.extra["olvl"]
-            n, h, w = self.grid[olvl]
-            P = self.P[olvl]
-            pre = self.bufs[L.pre]
-            fused = L.extra["fused"]
             if side is not None and ORDER_EVERY and b >= ORDER_EVERY and b % ORDER_EVERY == 0 and b < self.slots:
                 # ordering edge only (no buffer is reused): see ORDER_EVERY
                 wait_done(rev[b - ORDER_EVERY])
-            dyp, pws = L.extra["dyp"], L.extra["pws"]
+            pws = S.pws
             # unfused: the PReLU-backward pass leaves its dalpha/dbias partials in
             # pws for this layer's rdn_wgrad_reduce to sum (no finalize launch);
             # gated-out: the previous layer's dgrad epilogue already did (below)
-            if fused or "gated_by" in L.extra:
-                rc = 0
-            else:
-                if side is not None and b >= self.slots:
-                    wait_done(rev[b - self.slots])
-                if L.ddst is None:
-                    tok = tr.start(info["prelu"]) if tr is not None else None
-                    rc = lib.rdn_prelu_bwd(self.code, P, n, h, w, L.cout, L.cout_pad, None, 0, 0, 0, dy.data_ptr(),
-                                           pre.data_ptr(), pre.shape[1], self.named[L.act + ".weight"].data_ptr(),
-                                           dyp, None, None, pws, st)
-                else:
-                    dd_ptr, dd_ps, dd_c0, dd_pl = self._slice(L.ddst)
-                    tok = tr.start(info["prelu"]) if tr is not None else None
-                    rc = lib.rdn_prelu_bwd(self.code, P, n, h, w, L.cout, L.cout_pad, dd_ptr, dd_ps,
-                                           dd_c0, dd_pl, None, pre.data_ptr(), pre.shape[1],
-                                           self.named[L.act + ".weight"].data_ptr(), dyp, None, None, pws, st)
-                if tok is not None:
-                    tr.stop(tok)
-            if rc:
-                H.check(rc, f"prelu_bwd[{L.name}]")
-            dw = L.extra["dw"]
+            if S.gate == GATE_PRELU:
+                wait_slot(b)
+                n, h, w = self.grid[S.olvl]
+                pre = self.bufs[L.pre]
+                dy_src = (None, 0, 0, 0, dy.data_ptr()) if L.ddst is None else (*self._slice(L.ddst), None)
+                launch(info["prelu"], "prelu_bwd", L, lib.rdn_prelu_bwd, self.code, self.P[S.olvl], n, h, w, L.cout,
+                       L.cout_pad, *dy_src, pre.data_ptr(), pre.shape[1], self.named[L.act + ".weight"].data_ptr(),
+                       S.dyp, None, None, pws, st)
+            K = S.gates   # (gate-out) this layer's dgrad epilogue writes K's dYpre / partials into K's ring slot
             if dw:
                 # fused input + weight gradient on the compute stream; its slabs and
                 # partials go to this ring slot's buffers, free once the side stream
                 # reduced the layer that used the slot before
-                if side is not None and b >= self.slots:
-                    wait_done(rev[b - self.slots])
-                K = L.extra.get("gates")
-                if K is not None and side is not None and K.extra["bidx"] >= self.slots:
-                    # (gate-out) this epilogue writes K's dYpre / partials into K's ring slot
-                    wait_done(rev[K.extra["bidx"] - self.slots])
-                tok = tr.start(info["dw"]) if tr is not None else None
-                rc = lib.rdn_conv_dgrad_wgrad(C.byref(L.dgrad_desc), C.byref(L.wgrad_desc), st)
-                if tok is not None:
-                    tr.stop(tok)
-                if rc:
-                    H.check(rc, f"dgrad_wgrad[{L.name}]")
+                wait_slot(b)
+                if K is not None:
+                    wait_slot(K.bwd.bidx)
+                launch(info["dw"], "dgrad_wgrad", L, lib.rdn_conv_dgrad_wgrad, C.byref(L.dgrad_desc),
+                       C.byref(L.wgrad_desc), st)
                 if side is not None:
-                    L.extra["ev_ready"].record(main)
+                    S.ev_ready.record(main)
             else:
                 if side is not None:
-                    L.extra["ev_ready"].record(main)
-                K = L.extra.get("gates")
-                if K is not None and side is not None and K.extra["bidx"] >= self.slots:
-                    # this epilogue writes K's dYpre / partials into K's ring slot
-                    wait_done(rev[K.extra["bidx"] - self.slots])
+                    S.ev_ready.record(main)
+                if K is not None:
+                    wait_slot(K.bwd.bidx)
                 if L.src.buf not in self.pure_inputs or need_buf[L.src.buf]:
-                    tok = tr.start(info["dgrad"]) if tr is not None else None
-                    rc = lib.rdn_conv_fwd(C.byref(L.dgrad_desc), st)
-                    if tok is not None:
-                        tr.stop(tok)
-                    if rc:
-                        H.check(rc, f"dgrad[{L.name}]")
+                    launch(info["dgrad"], "dgrad", L, lib.rdn_conv_fwd, C.byref(L.dgrad_desc), st)
             # stream of this layer's reduce: a fused layer's right behind its kernel on
             # the main stream (interleaved step A/B 1652 vs 1636 img/s on the side
             # stream -- at level 0 the side stream has nothing else to overlap)
-            rst = sst
-            if dw:
-                rst = st
-            elif side is not None:
-                side.wait_event(L.extra["ev_ready"])
+            rst = st if dw else sst
             if not dw:
+                if side is not None:
+                    side.wait_event(S.ev_ready)
                 if fused and batch_side and b >= self.slots and any(Lp is rev[b - self.slots] for Lp, _ in spending):
                     # a fused wgrad writes its dalpha/dbias partials into this ring slot from
                     # the side stream and never passes wait_done: the slot's previous layer
                     # must not still sit in the batch (its reduce reads those partials);
                     # launched first, the side stream's order does the rest
                     flush_side()
-                tok = tr.start(info["wgrad"], side) if tr is not None else None
-                rc = lib.rdn_conv_wgrad(C.byref(L.wgrad_desc), sst)
-                if tok is not None:
-                    tr.stop(tok)
-                if rc:
-                    H.check(rc, f"wgrad[{L.name}]")
-            splits, mdim, ndim, ndim_real, taps = L.extra["wgrad"]
-            part_splits = (0 if fused else L.extra["part_rows"] if "gated_by" in L.extra
-                           else lib.rdn_prelu_bwd_blocks(self.code, P, L.cout_pad))
-            ow, ob, oa = L.extra["goff"]
-            cols = L.extra["dw_cols"]
+                launch(info["wgrad"], "wgrad", L, lib.rdn_conv_wgrad, C.byref(L.wgrad_desc), sst, on=(side,))
+            splits, mdim, ndim, ndim_real, taps = S.wgrad
+            part_splits = S.part_rows
+            ow, ob, oa = S.goff
+            cols = S.dw_cols
+            nh = ndim // cols   # column parts of the fused kernel: each part's slabs hold its
+            sh = splits // nh   # input channels; the dalpha/dbias partials are part 0's rows
             if dw and REDUCE_BATCH:
                 # (a fused layer's reduce joins the batch of consecutive fused layers,
                 # one launch on the compute stream: flushed before the next unfused layer)
                 jobs = []
-                nh = ndim // cols
-                sh = splits // nh
                 for hh in range(nh):
                     jobs.append(H.ReduceJob(
                         ws=L.wgrad_desc.ws + hh * sh * mdim * taps * cols * 4, grad=gbase + ow,
@@ -1390,10 +1386,7 @@ class UNetEngine:
                 if len(spending) >= min(self.side_batch, H.REDUCE_BATCH_MAX):
                     flush_side()
                 continue
-            if cols < ndim:
-                # column halves of the fused kernel: each half's slabs hold its input
-                # channels; the dalpha/dbias partials are half 0's rows
-                nh, sh = ndim // cols, splits // (ndim // cols)
+            if nh > 1:
                 for hh in range(nh):
                     rc = lib.rdn_wgrad_reduce_cols(L.wgrad_desc.ws + hh * sh * mdim * taps * cols * 4, sh, mdim, cols,
                                                    taps, gbase + ow, ndim_real, hh * cols, 1,
@@ -1407,9 +1400,9 @@ class UNetEngine:
             if rc:
                 H.check(rc, f"wgrad_reduce[{L.name}]")
             if side is not None:
-                L.extra["ev_done"].record(main if rst == st else side)
+                S.ev_done.record(main if rst == st else side)
             if sync is not None:   # the stream this layer's gradients were completed on
-                sync.params_done(L.extra["pidx"], stream=None if side is None else (main if rst == st else side))
+                sync.params_done(S.pidx, stream=None if side is None else (main if rst == st else side))
         flush()
         flush_side()
         if side is not None:

@@ -217,3 +217,64 @@ def test_conv_layer_extra_is_a_read_only_view_of_the_typed_state():
             del L.extra["info"]
         with pytest.raises(AttributeError):
             L.extra = {}
+
+
+def test_reduce_entries_share_one_argument_check():
+    """The three reduce entries reject a bad job before anything is launched (no GPU
+    needed), with the calling entry and the job index in the error text."""
+    import ctypes
+    from vub_image_denoising_amd import _hip as H
+    lib = H.load_library()
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 16   # 16-byte aligned, never dereferenced
+    assert lib.rdn_wgrad_reduce(p, 2, 16, 6, 3, 9, p, 0, None, 0, None, None, None) == -1     # ndim % 4
+    assert b"rdn_wgrad_reduce: job 0" in lib.rdn_last_error()
+    assert lib.rdn_wgrad_reduce_cols(p, 2, 16, 32, 9, p, 96, 80, 0, None, 0, None, None, None) == -1   # past gstride
+    assert b"rdn_wgrad_reduce_cols: job 0" in lib.rdn_last_error()
+    good = dict(ws=p, grad=p, splits=2, mdim=16, ndim=8, ndim_real=3, taps=9, gstride=3)
+    jobs = (H.ReduceJob * 2)(H.ReduceJob(**good), H.ReduceJob(**{**good, "splits": 0}))
+    assert lib.rdn_wgrad_reduce_batch(jobs, 2, None) == -1
+    assert b"rdn_wgrad_reduce_batch: job 1" in lib.rdn_last_error()
+    assert lib.rdn_wgrad_reduce_batch(jobs, H.REDUCE_BATCH_MAX + 1, None) == -1
+    assert b"1..8 jobs" in lib.rdn_last_error()
+
+
+def test_reduce_jobs_tile_the_layer_gradient():
+    """``engine.reduce_jobs`` (the one place with the column-part arithmetic): a plain
+    layer is one job over all its slabs; a fused layer in nh column parts is nh jobs whose
+    columns [gci0, gci0 + ndim_real) tile [0, ndim_real of the layer) without gap or
+    overlap, whose slab pointers advance by sh * mdim * taps * cols floats, of which only
+    part 0 carries the dalpha/dbias partials, and which sum sh partial rows when the
+    kernel gates in its loader (a row per slab of part 0), else the PReLU pass's rows."""
+    from vub_image_denoising_amd.engine import GATE_LOADER, GATE_PRELU, LayerBwd, reduce_jobs
+
+    WS, GBASE, PWS, GOFF = 0x10000, 0x7000000, 0x5000, [256, 8192, 8448]
+
+    def jobs(splits, mdim, ndim, ndim_real, taps, cols, gate, part_rows):
+        S = LayerBwd(3, 1, 4096, 0, [0, 1, 2], GOFF, gate=gate, dw=cols < ndim or gate == GATE_LOADER,
+                     wgrad=(splits, mdim, ndim, ndim_real, taps), dw_cols=cols, part_rows=part_rows, pws=PWS)
+        out = reduce_jobs(S, WS, GBASE)
+        for j in out:   # every job writes this layer's three gradients, accumulating
+            assert (j.grad, j.dbias, j.dalpha) == (GBASE + GOFF[0], GBASE + GOFF[1], GBASE + GOFF[2])
+            assert (j.mdim, j.taps, j.gstride, j.accumulate) == (mdim, taps, ndim_real, 1)
+            assert (j.sl, j.blocks, j.pblocks) == (0, 0, 0)   # the library's to fill
+        return out
+
+    # plain layers: a side-stream 3x3 with padded columns (PReLU pass: 37 rows), a loader-gated
+    # stride-2 one (part_splits 0: as many rows as splits)
+    for args, ps in (((12, 16, 8, 3, 9, 8, GATE_PRELU, 37), 37), ((20, 64, 32, 32, 4, 32, GATE_LOADER, 0), 0)):
+        (j,) = jobs(*args)
+        assert (j.ws, j.part, j.splits, j.ndim, j.ndim_real, j.gci0, j.part_splits) == (WS, PWS, args[0], args[2], args[3], 0, ps)
+
+    # h2 (64 = 2 x 32 columns) and h5 (160 = 5 x 32), loader-gated and pre-gated
+    for nh, splits in ((2, 512), (5, 1280)):
+        for gate, rows in ((GATE_LOADER, 0), (GATE_PRELU, 41)):
+            mdim, cols, taps = 32 if nh == 2 else 64, 32, 9
+            out = jobs(splits, mdim, nh * cols, nh * cols, taps, cols, gate, rows)
+            sh = splits // nh
+            assert len(out) == nh
+            assert [(j.gci0, j.gci0 + j.ndim_real) for j in out] == [(h * cols, (h + 1) * cols) for h in range(nh)]
+            assert [j.ws for j in out] == [WS + h * sh * mdim * taps * cols * 4 for h in range(nh)]
+            assert [j.part for j in out] == [PWS] + [None] * (nh - 1)
+            assert all((j.splits, j.ndim, j.ndim_real) == (sh, cols, cols) for j in out)
+            assert all(j.part_splits == (sh if gate == GATE_LOADER else rows) for j in out)

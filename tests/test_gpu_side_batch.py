@@ -113,7 +113,7 @@ def _check(monkeypatch, side_batch, slots, dtype):
     assert any(not torch.equal(grads[3][n], grads[2][n]) for n in grads[2]), "mirrored input: same gradients"
     for jobs in per_bwd:
         if side_batch == 1:
-            assert jobs == [], f"SIDE_BATCH=1 used the batch entry on the side stream: {jobs}"
+            assert jobs == [1] * n_side, f"SIDE_BATCH=1: not one reduce launch per layer on the side stream: {jobs}"
             continue
         assert sum(jobs) == n_side and all(1 <= j <= side_batch for j in jobs), jobs
         early = [j for j in jobs[:-1] if j < side_batch]

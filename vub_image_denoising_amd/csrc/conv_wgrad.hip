@@ -253,20 +253,11 @@ __device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ ws,
   }
 }
 
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, int splits, int mdim, int ndim,
-                                                           int ndim_real, int taps, float* __restrict__ grad,
-                                                           int accumulate, int sl_count, const float* __restrict__ part,
-                                                           int part_splits, float* __restrict__ dalpha,
-                                                           float* __restrict__ dbias, int gstride, int gci0) {
-  wgrad_reduce_block(ws, splits, mdim, ndim, ndim_real, taps, grad, accumulate, sl_count, part, part_splits, dalpha,
-                     dbias, gstride, gci0, blockIdx.x, blockIdx.y == 1);
-}
-
-// Several reductions in ONE launch (round 4): the fused dgrad+wgrad layers' reduces
-// run on the compute stream, one small latency-bound launch per layer (40 per B16
-// step, ~7 us each against ~2-3 us of slab bytes); consecutive ones go together.
-// Job j owns blocks [beg[j], beg[j+1]): its slab blocks, then its partial blocks.
-// Same per-block work and summation order as the single launches (bit-identical).
+// The reduce kernel: 1..RDN_REDUCE_BATCH_MAX reductions in ONE launch (round 4: a
+// layer's reduce is a small latency-bound launch, 40 per B16 step, ~7 us each against
+// ~2-3 us of slab bytes; consecutive ones go together).  Job j owns blocks
+// [beg[j], beg[j+1]): its slab blocks, then its partial blocks.  A job's per-block
+// work and summation order do not depend on its neighbours (bit-identical alone).
 struct ReduceBatch {
   rdn_reduce_job job[RDN_REDUCE_BATCH_MAX];
   int32_t beg[RDN_REDUCE_BATCH_MAX + 1];
@@ -389,47 +380,10 @@ static int reduce_lanes(int64_t total, int splits) {
   return sl;
 }
 
-static int wgrad_reduce_impl(const float* ws, int32_t splits, int32_t mdim, int32_t ndim, int32_t ndim_real,
-                             int32_t taps, float* grad, int32_t gstride, int32_t gci0, int32_t accumulate,
-                             const float* part, int32_t part_splits, float* dalpha, float* dbias, void* stream) {
-  if (!ws || !grad || splits <= 0 || mdim <= 0 || ndim <= 0 || ndim_real <= 0 || ndim_real > ndim || taps <= 0 ||
-      gci0 < 0 || gci0 + ndim_real > gstride) {
-    rdn_set_error("rdn_wgrad_reduce: bad arguments"); return RDN_E_ARG;
-  }
-  const int64_t total = (int64_t)mdim * ndim * taps;
-  if (ndim % 4 || ((uintptr_t)ws & 15)) { rdn_set_error("rdn_wgrad_reduce: ndim %% 4 / alignment"); return RDN_E_ARG; }
-  const int sl = reduce_lanes(total, splits);
-  const int qpb = 256 / sl;
-  int64_t blocks = (total / 4 + qpb - 1) / qpb;
-  if (part && blocks < 2 * mdim) blocks = 2 * mdim;
-  if (blocks > 0x7fffffff) { rdn_set_error("rdn_wgrad_reduce: too large"); return RDN_E_SHAPE; }
-  dim3 grid((unsigned)blocks, part ? 2 : 1);
-  wgrad_reduce_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(ws, splits, mdim, ndim, ndim_real, taps, grad, accumulate,
-                                                            sl, part, part_splits > 0 ? part_splits : splits, dalpha,
-                                                            dbias, gstride, gci0);
-  return rdn_check_launch("rdn_wgrad_reduce");
-}
-
-extern "C" int rdn_wgrad_reduce(const float* ws, int32_t splits, int32_t mdim, int32_t ndim, int32_t ndim_real,
-                                int32_t taps, float* grad, int32_t accumulate, const float* part, int32_t part_splits,
-                                float* dalpha, float* dbias, void* stream) {
-  return wgrad_reduce_impl(ws, splits, mdim, ndim, ndim_real, taps, grad, ndim_real, 0, accumulate, part, part_splits,
-                           dalpha, dbias, stream);
-}
-
-extern "C" int rdn_wgrad_reduce_cols(const float* ws, int32_t splits, int32_t mdim, int32_t ndim, int32_t taps,
-                                     float* grad, int32_t grad_ci_total, int32_t grad_ci0, int32_t accumulate,
-                                     const float* part, int32_t part_splits, float* dalpha, float* dbias,
-                                     void* stream) {
-  return wgrad_reduce_impl(ws, splits, mdim, ndim, ndim, taps, grad, grad_ci_total, grad_ci0, accumulate, part,
-                           part_splits, dalpha, dbias, stream);
-}
-
-// Up to RDN_REDUCE_BATCH_MAX reductions (each as rdn_wgrad_reduce_cols would run it:
-// ws, splits, mdim, ndim, ndim_real, taps, grad + gstride / gci0, accumulate, the
-// fused-PReLU partials) in one launch; sl / blocks are filled in here.
-extern "C" int rdn_wgrad_reduce_batch(const rdn_reduce_job* jobs, int32_t n, void* stream) {
-  if (!jobs || n <= 0 || n > RDN_REDUCE_BATCH_MAX) { rdn_set_error("rdn_wgrad_reduce_batch: 1..%d jobs", RDN_REDUCE_BATCH_MAX); return RDN_E_ARG; }
+// The one reduce launch behind the three entries (``who``: the calling one): checks
+// every job, fills in its sl / blocks / pblocks and its first block of the grid.
+static int reduce_launch(const char* who, const rdn_reduce_job* jobs, int32_t n, void* stream) {
+  if (!jobs || n <= 0 || n > RDN_REDUCE_BATCH_MAX) { rdn_set_error("%s: 1..%d jobs", who, RDN_REDUCE_BATCH_MAX); return RDN_E_ARG; }
   ReduceBatch b{};
   b.n = n;
   int64_t acc = 0;
@@ -437,20 +391,43 @@ extern "C" int rdn_wgrad_reduce_batch(const rdn_reduce_job* jobs, int32_t n, voi
     rdn_reduce_job q = jobs[j];
     if (!q.ws || !q.grad || q.splits <= 0 || q.mdim <= 0 || q.ndim <= 0 || q.ndim_real <= 0 || q.ndim_real > q.ndim ||
         q.taps <= 0 || q.gci0 < 0 || q.gci0 + q.ndim_real > q.gstride || q.ndim % 4 || ((uintptr_t)q.ws & 15)) {
-      rdn_set_error("rdn_wgrad_reduce_batch: job %d: bad arguments", j);
+      rdn_set_error("%s: job %d: bad arguments (or ndim %% 4 / ws alignment)", who, j);
       return RDN_E_ARG;
     }
     const int64_t total = (int64_t)q.mdim * q.ndim * q.taps;
     q.sl = reduce_lanes(total, q.splits);
     const int qpb = 256 / q.sl;
-    q.blocks = (int32_t)((total / 4 + qpb - 1) / qpb);
+    const int64_t blocks = (total / 4 + qpb - 1) / qpb;
     q.pblocks = q.part ? 2 * q.mdim : 0;
+    if (acc + blocks + q.pblocks > 0x7fffffff) { rdn_set_error("%s: job %d: too large", who, j); return RDN_E_SHAPE; }
+    q.blocks = (int32_t)blocks;
     b.job[j] = q;
     b.beg[j] = (int32_t)acc;
-    acc += (int64_t)q.blocks + q.pblocks;
+    acc += blocks + q.pblocks;
   }
-  if (acc > 0x7fffffff) { rdn_set_error("rdn_wgrad_reduce_batch: too large"); return RDN_E_SHAPE; }
   b.beg[n] = (int32_t)acc;
   wgrad_reduce_batch_kernel<<<(unsigned)acc, 256, 0, (hipStream_t)stream>>>(b);
-  return rdn_check_launch("rdn_wgrad_reduce_batch");
+  return rdn_check_launch(who);
+}
+
+// the single reductions are one-job batches (job fields in rdn_reduce_job's order)
+extern "C" int rdn_wgrad_reduce(const float* ws, int32_t splits, int32_t mdim, int32_t ndim, int32_t ndim_real,
+                                int32_t taps, float* grad, int32_t accumulate, const float* part, int32_t part_splits,
+                                float* dalpha, float* dbias, void* stream) {
+  const rdn_reduce_job q = {ws, grad, part, dalpha, dbias, splits, mdim, ndim, ndim_real, taps,
+                            /*gstride*/ ndim_real, /*gci0*/ 0, accumulate, part_splits};
+  return reduce_launch("rdn_wgrad_reduce", &q, 1, stream);
+}
+
+extern "C" int rdn_wgrad_reduce_cols(const float* ws, int32_t splits, int32_t mdim, int32_t ndim, int32_t taps,
+                                     float* grad, int32_t grad_ci_total, int32_t grad_ci0, int32_t accumulate,
+                                     const float* part, int32_t part_splits, float* dalpha, float* dbias,
+                                     void* stream) {
+  const rdn_reduce_job q = {ws, grad, part, dalpha, dbias, splits, mdim, ndim, /*ndim_real*/ ndim, taps,
+                            grad_ci_total, grad_ci0, accumulate, part_splits};
+  return reduce_launch("rdn_wgrad_reduce_cols", &q, 1, stream);
+}
+
+extern "C" int rdn_wgrad_reduce_batch(const rdn_reduce_job* jobs, int32_t n, void* stream) {
+  return reduce_launch("rdn_wgrad_reduce_batch", jobs, n, stream);
 }

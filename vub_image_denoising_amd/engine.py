@@ -235,8 +235,9 @@ GATE_OUT_DW = os.environ.get("RDN_GATE_OUT_DW", "1") == "1"
 # each part's loader, the five parts gated the same tile five times: 143 vs 101 us per
 # launch at B16, profiles/r05_*); RDN_DW_PREGATED=0 gates in the loaders instead
 DW_PREGATED = os.environ.get("RDN_DW_PREGATED", "1") != "0"
-# the fused layers' split-K reduces of consecutive fused layers in one launch
-# (rdn_wgrad_reduce_batch; RDN_REDUCE_BATCH=0: one launch per layer)
+# every split-K reduce is a rdn_wgrad_reduce_batch launch (_ReduceQueue): those of
+# consecutive fused layers go in one launch on the compute stream
+# (RDN_REDUCE_BATCH=0: one launch per layer, its column parts as its jobs)
 REDUCE_BATCH = os.environ.get("RDN_REDUCE_BATCH", "1") != "0"
 # conv_0..conv_2 of every level-0 DenoisingBlock (base_filters 32, bf16) as ONE
 # launch that reads x once and keeps out_0 / out_1 on chip (rdn_dense3_fwd)
@@ -249,7 +250,7 @@ FUSE_DENSE1 = os.environ.get("RDN_DENSE1", "1") != "0"
 SPLITK = os.environ.get("RDN_SPLITK", "1") != "0"
 # round 6: the weight-gradient stream's split-K reduces of this many consecutive
 # layers in one rdn_wgrad_reduce_batch launch (each layer its own slab of a ring;
-# RDN_SIDE_BATCH=1: one reduce launch per layer, as before)
+# RDN_SIDE_BATCH=1: one one-job launch per layer, right behind its wgrad)
 SIDE_BATCH = max(1, min(8, int(os.environ.get("RDN_SIDE_BATCH", "4"))))
 # forward-only batches are run in chunks of at most this many pixels (run_unet)
 FWD_CHUNK_PIXELS = 1 << 23
@@ -369,6 +370,58 @@ class ConvLayer:
         v = {"info": self.info, "splitk": self.splitk or None, "dense3": self.dense3, "dw": S and S.dw,
              "gates": S and S.gates, "side_slab": S and S.side_slab}
         return MappingProxyType({k: x for k, x in v.items() if x is not None})
+
+
+def reduce_jobs(S: LayerBwd, ws: int, gbase: int) -> list:
+    """The split-K reduce of one layer's weight gradient (slabs at ``ws``) into the flat
+    gradient buffer at ``gbase``, as rdn_wgrad_reduce_batch jobs: one, or one per column
+    part of the fused kernel (each part's slabs hold ``dw_cols`` input channels; the
+    dalpha/dbias partials are part 0's rows).  Plain integers in, ctypes structs out."""
+    splits, mdim, ndim, ndim_real, taps = S.wgrad
+    ow, ob, oa = S.goff
+    cols = S.dw_cols
+    nh = ndim // cols
+    sh = splits // nh
+    jn, jr = (cols, cols) if nh > 1 else (ndim, ndim_real)
+    part_splits = sh if nh > 1 and S.gate == GATE_LOADER else S.part_rows
+    return [H.ReduceJob(ws=ws + hh * sh * mdim * taps * cols * 4, grad=gbase + ow, part=S.pws if hh == 0 else None,
+                        dalpha=gbase + oa, dbias=gbase + ob, splits=sh, mdim=mdim, ndim=jn, ndim_real=jr, taps=taps,
+                        gstride=ndim_real, gci0=hh * cols, accumulate=1, part_splits=part_splits)
+            for hh in range(nh)]
+
+
+class _ReduceQueue:
+    """Layers whose reduce jobs wait for one rdn_wgrad_reduce_batch launch on ``st``
+    (``stream``: its torch stream when the pass has a side stream, else None); ``cap``
+    layers fill it (None: flushed by the sweep only)."""
+    __slots__ = ("st", "stream", "cap", "sync", "layers", "jobs")
+
+    def __init__(self, st, stream, cap, sync):
+        self.st, self.stream, self.cap, self.sync = st, stream, cap, sync
+        self.layers, self.jobs = [], []
+
+    def holds(self, L):
+        return any(Lp is L for Lp in self.layers)
+
+    def add(self, L, jobs):
+        self.layers.append(L)
+        self.jobs += jobs
+        if self.cap is not None and len(self.layers) >= self.cap:
+            self.flush()
+
+    def flush(self):
+        jl, fn = self.jobs, H.lib().rdn_wgrad_reduce_batch
+        for i in range(0, len(jl), H.REDUCE_BATCH_MAX):
+            n = min(H.REDUCE_BATCH_MAX, len(jl) - i)
+            rc = fn((H.ReduceJob * n)(*jl[i:i + n]), n, self.st)
+            if rc:
+                H.check(rc, f"wgrad_reduce_batch[{self.layers[0].name}..{self.layers[-1].name}]")
+        for L in self.layers:   # slot free / gradients complete, on the stream that reduced them
+            if self.stream is not None:
+                L.bwd.ev_done.record(self.stream)
+            if self.sync is not None:
+                self.sync.params_done(L.bwd.pidx, stream=self.stream)
+        self.layers, self.jobs = [], []
 
 
 @dataclass
@@ -1256,46 +1309,23 @@ class UNetEngine:
             self.ev_begin.record(main)
             side.wait_event(self.ev_begin)   # gradient buffer zeroed
         else:
-            sst = st
+            main, sst = None, st
         launch = self._launch
         rev = list(reversed(self.layers))
-        pending = []   # fused layers whose split-K reduces wait for one batched launch
-        spending = []  # weight-gradient-stream layers whose reduces wait for one batched launch
+        # split-K reduces waiting for a batched launch: the fused layers' on the compute
+        # stream (consecutive ones: flushed before the next unfused layer), the others'
+        # on the weight-gradient stream (this pass's: none under SERIAL_BWD)
         batch_side = side is not None and self.side_batch > 1
-
-        def flush_side():
-            if not spending:
-                return
-            jl = [j for _, j in spending]
-            H.check(lib.rdn_wgrad_reduce_batch((H.ReduceJob * len(jl))(*jl), len(jl), sst), "wgrad_reduce_batch(side)")
-            for Lp, _ in spending:
-                Lp.bwd.ev_done.record(side)
-                if sync is not None:
-                    sync.params_done(Lp.bwd.pidx, stream=side)
-            spending.clear()
-
-        def flush():
-            if not pending:
-                return
-            jl = [j for _, js in pending for j in js]
-            for i in range(0, len(jl), H.REDUCE_BATCH_MAX):
-                n_ = min(H.REDUCE_BATCH_MAX, len(jl) - i)
-                H.check(lib.rdn_wgrad_reduce_batch((H.ReduceJob * n_)(*jl[i:i + n_]), n_, st), "wgrad_reduce_batch")
-            for Lp, _ in pending:
-                if side is not None:
-                    Lp.bwd.ev_done.record(main)
-                if sync is not None:
-                    sync.params_done(Lp.bwd.pidx, stream=None if side is None else main)
-            pending.clear()
+        cq = _ReduceQueue(st, main, None if REDUCE_BATCH else 1, sync)
+        sq = _ReduceQueue(sst, side, min(self.side_batch, H.REDUCE_BATCH_MAX) if batch_side else 1, sync)
 
         def wait_done(Lw):
             """The compute stream waits for layer Lw's weight-gradient work (its slot
             free / an ordering edge); a still-batched layer is flushed first, so its
             event is recorded in this pass before the wait."""
-            if any(Lp is Lw for Lp, _ in pending):
-                flush()
-            if any(Lp is Lw for Lp, _ in spending):
-                flush_side()
+            for q in (cq, sq):
+                if q.holds(Lw):
+                    q.flush()
             main.wait_event(Lw.bwd.ev_done)
 
         def wait_slot(bi):
@@ -1307,8 +1337,8 @@ class UNetEngine:
         for b, L in enumerate(rev):
             S, info = L.bwd, L.info
             dw, fused = S.dw, S.gate == GATE_LOADER
-            if pending and not dw:
-                flush()
+            if cq.layers and not dw:
+                cq.flush()
             if side is not None and ORDER_EVERY and b >= ORDER_EVERY and b % ORDER_EVERY == 0 and b < self.slots:
                 # ordering edge only (no buffer is reused): see ORDER_EVERY
                 wait_done(rev[b - ORDER_EVERY])
@@ -1343,68 +1373,22 @@ class UNetEngine:
                     wait_slot(K.bwd.bidx)
                 if L.src.buf not in self.pure_inputs or need_buf[L.src.buf]:
                     launch(info["dgrad"], "dgrad", L, lib.rdn_conv_fwd, C.byref(L.dgrad_desc), st)
-            # stream of this layer's reduce: a fused layer's right behind its kernel on
-            # the main stream (interleaved step A/B 1652 vs 1636 img/s on the side
-            # stream -- at level 0 the side stream has nothing else to overlap)
-            rst = st if dw else sst
             if not dw:
                 if side is not None:
                     side.wait_event(S.ev_ready)
-                if fused and batch_side and b >= self.slots and any(Lp is rev[b - self.slots] for Lp, _ in spending):
+                if fused and batch_side and b >= self.slots and sq.holds(rev[b - self.slots]):
                     # a fused wgrad writes its dalpha/dbias partials into this ring slot from
                     # the side stream and never passes wait_done: the slot's previous layer
                     # must not still sit in the batch (its reduce reads those partials);
                     # launched first, the side stream's order does the rest
-                    flush_side()
+                    sq.flush()
                 launch(info["wgrad"], "wgrad", L, lib.rdn_conv_wgrad, C.byref(L.wgrad_desc), sst, on=(side,))
-            splits, mdim, ndim, ndim_real, taps = S.wgrad
-            part_splits = S.part_rows
-            ow, ob, oa = S.goff
-            cols = S.dw_cols
-            nh = ndim // cols   # column parts of the fused kernel: each part's slabs hold its
-            sh = splits // nh   # input channels; the dalpha/dbias partials are part 0's rows
-            if dw and REDUCE_BATCH:
-                # (a fused layer's reduce joins the batch of consecutive fused layers,
-                # one launch on the compute stream: flushed before the next unfused layer)
-                jobs = []
-                for hh in range(nh):
-                    jobs.append(H.ReduceJob(
-                        ws=L.wgrad_desc.ws + hh * sh * mdim * taps * cols * 4, grad=gbase + ow,
-                        part=pws if hh == 0 else None, dalpha=gbase + oa, dbias=gbase + ob,
-                        splits=sh, mdim=mdim, ndim=cols if nh > 1 else ndim, ndim_real=cols if nh > 1 else ndim_real,
-                        taps=taps, gstride=ndim_real, gci0=hh * cols, accumulate=1,
-                        part_splits=sh if (nh > 1 and fused) else part_splits))
-                pending.append((L, jobs))
-                continue
-            if batch_side and not dw:
-                # the weight-gradient stream's reduce joins the batch of consecutive such
-                # layers (their slabs are distinct ring entries: side_slab)
-                spending.append((L, H.ReduceJob(
-                    ws=L.wgrad_desc.ws, grad=gbase + ow, part=pws, dalpha=gbase + oa, dbias=gbase + ob,
-                    splits=splits, mdim=mdim, ndim=ndim, ndim_real=ndim_real, taps=taps, gstride=ndim_real,
-                    gci0=0, accumulate=1, part_splits=part_splits)))
-                if len(spending) >= min(self.side_batch, H.REDUCE_BATCH_MAX):
-                    flush_side()
-                continue
-            if nh > 1:
-                for hh in range(nh):
-                    rc = lib.rdn_wgrad_reduce_cols(L.wgrad_desc.ws + hh * sh * mdim * taps * cols * 4, sh, mdim, cols,
-                                                   taps, gbase + ow, ndim_real, hh * cols, 1,
-                                                   pws if hh == 0 else None, sh if fused else part_splits,
-                                                   gbase + oa, gbase + ob, rst)
-                    if rc:
-                        break
-            else:
-                rc = lib.rdn_wgrad_reduce(L.wgrad_desc.ws, splits, mdim, ndim, ndim_real, taps, gbase + ow, 1, pws,
-                                          part_splits, gbase + oa, gbase + ob, rst)
-            if rc:
-                H.check(rc, f"wgrad_reduce[{L.name}]")
-            if side is not None:
-                S.ev_done.record(main if rst == st else side)
-            if sync is not None:   # the stream this layer's gradients were completed on
-                sync.params_done(S.pidx, stream=None if side is None else (main if rst == st else side))
-        flush()
-        flush_side()
+            # stream of this layer's reduce: a fused layer's right behind its kernel on
+            # the main stream (interleaved step A/B 1652 vs 1636 img/s on the side
+            # stream -- at level 0 the side stream has nothing else to overlap)
+            (cq if dw else sq).add(L, reduce_jobs(S, L.wgrad_desc.ws, gbase))
+        cq.flush()
+        sq.flush()
         if side is not None:
             self.ev_end.record(side)
             main.wait_event(self.ev_end)

@@ -387,6 +387,32 @@ int64_t rdn_image_metrics_workspace_size(int32_t n, int32_t c, int32_t h, int32_
 int rdn_image_metrics(const float* gt, const float* x, int32_t n, int32_t c, int32_t h, int32_t w,
                       float data_range, double* ws, double* psnr, double* ssim, void* stream);
 
+/* Whole images of any size through a network of one fixed input shape: overlapping tiles
+   (no reference counterpart: the reference evaluates 256x256 blocks only).  Per axis, for
+   extent n, requested tile and overlap:
+     t    = min(tile, ceil8(n))              tile extent on this axis
+     npad = max(n, t)                        > n only when n < t; then npad - n <= 7
+     s    = t - overlap
+     k    = 0 if npad == t else ceil((npad - t) / s)
+     o_i  = min(i*s, npad - t), i = 0..k     the last tile is clamped to end at npad
+   A padded position p >= n reads source 2*(n-1) - p (torch 'reflect').  Tiles are ordered
+   image b, then ky, then kx: global index (b*ny + ky)*nx + kx.  Blend window per axis
+   w(i) = min(1, min(i+1, t-i) / (overlap+1)) (fp32 division), 2-D weight wy*wx.
+   Valid: tile % 8 == 0, tile >= 16, 0 <= overlap <= tile/2, h, w >= 8 (<= 2^23),
+   1 <= c <= 8; anything else returns RDN_E_ARG before any launch, the message naming the
+   argument.  A pixel is covered by at most 3 tiles per axis. */
+int rdn_tile_grid(int32_t h, int32_t w, int32_t tile, int32_t overlap, int32_t out[4] /* th, tw, ny, nx */);
+/* tiles[j] = tile first+j of img [n, c, h, w] (fp32 NCHW), j < count: a bit-exact copy
+   with reflect indexing.  An index past the last tile repeats the last tile, so the final
+   batch of a fixed batch shape is complete. */
+int rdn_tile_gather(const float* img, int32_t n, int32_t c, int32_t h, int32_t w, int32_t tile, int32_t overlap,
+                    int64_t first, int32_t count, float* tiles /* [count, c, th, tw] */, void* stream);
+/* out = sum(wy*wx*v) / sum(wy*wx) over the tiles covering each pixel, in ascending ky then
+   kx, in fp32 (no atomics: deterministic); a pixel covered by exactly one tile takes that
+   tile's value unchanged.  Padded positions are not written. */
+int rdn_tile_blend(const float* tiles /* [n*ny*nx, c, th, tw] */, int32_t n, int32_t c, int32_t h, int32_t w,
+                   int32_t tile, int32_t overlap, float* out /* [n, c, h, w] */, void* stream);
+
 const char* rdn_version(void);
 const char* rdn_last_error(void);
 

@@ -44,7 +44,7 @@ def init_weights(init_type='xavier'):
     return initializer
 
 
-_RUNTIME = ("_rdn_flat", "_rdn_packs", "_rdn_engines", "_rdn_prog")
+_RUNTIME = ("_rdn_flat", "_rdn_packs", "_rdn_engines", "_rdn_prog", "_rdn_tile_graphs")
 
 
 class _GpuBlock:

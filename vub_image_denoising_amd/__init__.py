@@ -16,5 +16,6 @@ from .Unet_model import (DenoisingBlock, DownsampleBlock, InputBlock, OutputBloc
 from .RDUNet_model import RDUNet  # noqa: F401
 from .diffusion_RDUnet import (DiffusionModel, charbonnier_loss, combined_loss, denormalize,  # noqa: F401
                                sample_biased, train_step_checkpointed, train_model_checkpointed, load_checkpoint)
+from .sampling import denoise_tiled, plan_tiles  # noqa: F401
 
 __version__ = "0.1.0"

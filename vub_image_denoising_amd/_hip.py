@@ -138,6 +138,9 @@ SIGNATURES = {
     "rdn_synth_batch": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdn_image_metrics_workspace_size": (_i64, [_i32, _i32, _i32, _i32]),
     "rdn_image_metrics": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp]),
+    "rdn_tile_grid": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(_i32)]),
+    "rdn_tile_gather": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _vp]),
+    "rdn_tile_blend": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "rdn_version": (C.c_char_p, []),
     "rdn_last_error": (C.c_char_p, []),
 }

@@ -56,6 +56,11 @@ class DiffusionModel(nn.Module):
         t = torch.tensor([1.0], device=noisy_image.device).unsqueeze(0).unsqueeze(2).unsqueeze(3)
         return self.unet(noisy_image, t)
 
+    def denoise_image(self, noisy_image, **kw):
+        """Whole images of any size by overlapping tiles (sampling.denoise_tiled)."""
+        from .sampling import denoise_tiled
+        return denoise_tiled(self, noisy_image, **kw)
+
     def forward(self, clean_image, noisy_image, t):
         noisy_step_image = self.forward_diffusion(clean_image, noisy_image, t)
         return self.improved_sampling(noisy_step_image)

@@ -18,11 +18,17 @@ MI355X-first changes, each bit-exact:
   one hipGraph;
 * optional ``skip_zero_weight``: at t = T the reference multiplies f1 by
   (1 - a) = 0 (:45); skipping that call changes nothing unless f1 is not finite.
+
+``denoise_tiled`` (no reference counterpart) runs either sampler over whole images of
+any size: overlapping tiles of one fixed shape through one captured SamplerGraph,
+gathered and blended by ``rdn_tile_gather`` / ``rdn_tile_blend``.
 """
 from __future__ import annotations
 
 import torch
 
+from . import _hip as H
+from . import engine as E
 from . import functional as Fn
 
 
@@ -112,6 +118,113 @@ class SamplerGraph:
             packs.refresh()
         self.graph.replay()
         return self.out
+
+
+# ----------------------------------------------------------------- whole images by tiles
+def _plan_axis(n, tile, overlap):
+    """One axis of the tile grid (include/rdunet_hip.h, rdn_tile_grid): tile extent and origins."""
+    t = min(tile, (n + 7) // 8 * 8)
+    npad = max(n, t)
+    if npad == t:
+        return t, [0]
+    s = t - overlap
+    k = -((t - npad) // s)            # ceil((npad - t) / s)
+    return t, [min(i * s, npad - t) for i in range(k + 1)]
+
+
+def plan_tiles(H, W, tile, overlap):
+    """The tile grid of an H x W image: ``th, tw, ys, xs`` -- the tile shape and the tiles'
+    row / column origins in the image padded (reflect, bottom / right) to at least one tile.
+    The same definition as ``rdn_tile_grid``; tile ``(ky, kx)`` of image ``b`` has the
+    global index ``(b*len(ys) + ky)*len(xs) + kx``."""
+    if tile % 8 or tile < 16:
+        raise ValueError(f"tile must be a multiple of 8 and >= 16, got {tile}")
+    if not 0 <= overlap <= tile // 2:
+        raise ValueError(f"overlap must be in [0, tile/2], got {overlap} for tile {tile}")
+    if H < 8 or W < 8:
+        raise ValueError(f"image must be at least 8x8, got {H}x{W}")
+    th, ys = _plan_axis(H, tile, overlap)
+    tw, xs = _plan_axis(W, tile, overlap)
+    return th, tw, ys, xs
+
+
+def tile_gather(img, tile, overlap, first, count, out=None):
+    """Tiles ``first .. first+count-1`` of ``img`` [B,C,H,W] as [count,C,th,tw]; an index
+    past the last tile repeats the last tile (``rdn_tile_gather``)."""
+    H.require_device(img)
+    B, C, Hh, Ww = img.shape
+    th, tw, _, _ = plan_tiles(Hh, Ww, tile, overlap)
+    if out is None:
+        out = torch.empty((count, C, th, tw), dtype=torch.float32, device=img.device)
+    H.check(H.lib().rdn_tile_gather(img.data_ptr(), B, C, Hh, Ww, tile, overlap, first, count, out.data_ptr(),
+                                    H.stream_ptr()), "tile_gather")
+    return out
+
+
+def tile_blend(tiles, out, tile, overlap):
+    """Blend all tiles [B*ny*nx,C,th,tw] of the grid of ``out`` [B,C,H,W] into ``out``
+    (``rdn_tile_blend``)."""
+    H.require_device(tiles, out)
+    B, C, Hh, Ww = out.shape
+    th, tw, ys, xs = plan_tiles(Hh, Ww, tile, overlap)
+    if tuple(tiles.shape) != (B * len(ys) * len(xs), C, th, tw):
+        raise RuntimeError(f"tile_blend: expected tiles {(B * len(ys) * len(xs), C, th, tw)}, got {tuple(tiles.shape)}")
+    H.check(H.lib().rdn_tile_blend(tiles.data_ptr(), B, C, Hh, Ww, tile, overlap, out.data_ptr(), H.stream_ptr()),
+            "tile_blend")
+    return out
+
+
+def _tile_sampler(model, shape, sampler, graph):
+    """The sampler for tile batches of ``shape``: eager, or the model's cached SamplerGraph."""
+    direct = sampler == "direct"
+    if not graph:
+        return model.direct_sampling if direct else (lambda x: improved_sampling(model, x))
+    unet = model.unet
+    E.flat_params(unet, next(unet.parameters()).device)     # (re)creates the runtime state if it is stale
+    cache = unet.__dict__.setdefault("_rdn_tile_graphs", {})
+    # what a capture depends on besides the tile batch shape and the sampler
+    key = (shape[2], shape[3], shape[0], sampler, shape[1], model.timesteps, unet.compute_dtype, unet.training)
+    hit = cache.get(key)
+    if hit is None or hit[0] is not unet._rdn_flat or hit[1].model is not model:
+        hit = cache[key] = (unet._rdn_flat, SamplerGraph(model, shape, direct=direct))
+    return hit[1]
+
+
+def denoise_tiled(model, noisy, *, tile=512, overlap=32, sampler="improved", tile_batch=None, graph=True):
+    """Denoise whole images of any size H, W >= 8: ``noisy`` [B,C,H,W] (device, fp32) is cut
+    into overlapping tiles of one shape (``plan_tiles``), ``tile_batch`` tiles at a time go
+    through the sampler (``improved_sampling`` or ``direct_sampling``), and the results are
+    blended back with a linear ramp over the overlap.  One engine and -- with ``graph`` --
+    one captured SamplerGraph, kept on the model, serve every image size; memory is bounded
+    by the tile batch.  A region covered by one tile is that tile's sampler output bit for
+    bit.  Tiling is not the untiled network: the receptive field is far wider than the
+    overlap, so results differ from an untiled run wherever there is more than one tile."""
+    if sampler not in ("improved", "direct"):
+        raise ValueError(f"sampler must be 'improved' or 'direct', got {sampler!r}")
+    if not isinstance(noisy, torch.Tensor) or noisy.dim() != 4:
+        raise RuntimeError("denoise_tiled: expected a [B,C,H,W] tensor")
+    H.require_device(noisy, next(model.parameters()))
+    x = noisy.contiguous().float()
+    B, C, Hh, Ww = x.shape
+    th, tw, ys, xs = plan_tiles(Hh, Ww, tile, overlap)
+    n_tiles = B * len(ys) * len(xs)
+    if tile_batch is None:
+        # the batched improved sampler runs 2B images: stay below run_unet's chunking threshold
+        k = 2 if sampler == "improved" else 1
+        tile_batch = max(1, min(n_tiles, E.FWD_CHUNK_PIXELS // (k * th * tw)))
+    if tile_batch < 1:
+        raise ValueError(f"tile_batch must be >= 1, got {tile_batch}")
+    with torch.no_grad():
+        run = _tile_sampler(model, (tile_batch, C, th, tw), sampler, graph)
+        tin = torch.empty((tile_batch, C, th, tw), dtype=torch.float32, device=x.device)
+        tout = torch.empty((n_tiles, C, th, tw), dtype=torch.float32, device=x.device)
+        out = torch.empty_like(x)
+        for first in range(0, n_tiles, tile_batch):
+            tile_gather(x, tile, overlap, first, tile_batch, out=tin)
+            m = min(tile_batch, n_tiles - first)
+            tout[first:first + m].copy_(run(tin)[:m])     # the surplus of the last batch is dropped
+        tile_blend(tout, out, tile, overlap)
+    return out
 
 
 class ForwardGraph:

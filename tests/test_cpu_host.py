@@ -73,6 +73,85 @@ def test_dense3_level_validation_on_host():
     assert lib.rdn_dense3_fwd(ctypes.byref(d), None) < 0 and b"H % 16" in lib.rdn_last_error()
 
 
+def _dw_pair(ck, ncols, nhw, gated=True, gout_c0=None):
+    """Descriptor pair of one fused dgrad + wgrad launch over fake, 16-byte aligned
+    pointers: bf16, `ck` dY channels, `ncols` input channels."""
+    from vub_image_denoising_amd import _hip as H
+    d, wg = H.ConvDesc(), H.WgradDesc()
+    d.dtype = wg.dtype = H.RDN_BF16
+    d.gather = wg.gather = H.RDN_G_CONV3
+    d.n, d.h, d.w = wg.n, wg.h, wg.w = nhw
+    d.hin, d.win = wg.hin, wg.win = nhw[1], nhw[2]
+    d.cin = wg.mdim = ck
+    d.ncols = d.cout = wg.ndim = ncols
+    d.kp = (9 * ck + 63) // 64 * 64
+    d.x = wg.a = 1 << 20
+    d.wp, d.out, wg.b, wg.ws = 2 << 20, 3 << 20, 4 << 20, 5 << 20
+    d.x_ps = wg.a_ps = ck
+    d.out_ps = wg.b_ps = ncols
+    if gated:
+        d.gate = wg.a_gate = 6 << 20
+        d.gate_alpha = wg.a_gate_alpha = 7 << 20
+        d.gate_ps = wg.a_gate_ps = ck
+        wg.part = 8 << 20
+    if gout_c0 is not None:
+        d.gout, d.gout_pre, d.gout_alpha, d.gout_part = 9 << 20, 10 << 20, 11 << 20, 12 << 20
+        d.gout_c0 = gout_c0
+        d.gout_ps = d.gout_pre_ps = ncols - gout_c0
+    return d, wg
+
+
+# (dY channels, input channels, variant) -> kernel, column parts; the variant is "" (gated),
+# "pregated" (no gate, no partials) or the first channel of a gate-out tail
+_DW_SERVED = (
+    [((ck, nc, ""), (f"conv3_dw_kernel<bf16,{nc},{ck}>", 1)) for ck in (16, 32) for nc in (32, 48, 64, 80)]
+    + [((32, 96, ""), ("conv3_dw_kernel<bf16,48,32,h2>", 2)),
+       ((32, 128, ""), ("conv3_dw_kernel<bf16,64,32,h2>", 2)),
+       ((64, 160, ""), ("conv3_dw_kernel<bf16,32,64,h5>", 5)),
+       ((64, 160, "pregated"), ("conv3_dw_kernel<bf16,32,64,h5,pregated>", 5)),
+       ((32, 96, 32), ("conv3_dw_kernel<bf16,48,32,h2,go>", 2)),
+       ((32, 64, 0), ("conv3_dw_kernel<bf16,64,32,go>", 1))])
+
+
+def test_fused_dgrad_wgrad_dispatch_table():
+    """The fused pair's host dispatch without a GPU: kernel name, split count, columns per
+    slab and gate-out partial rows of every served shape, and the pairs it leaves to the
+    separate kernels.  Split counts are those of a 256-CU device (what a failed device
+    query counts as): 8 x parts at one tile, min(256 / (8 parts), 8 tiles per XCD) x 8 x
+    parts at (2, 64, 64)."""
+    import ctypes
+    from vub_image_denoising_amd import _hip as H
+    lib = H.load_library()
+    cus256 = not torch.cuda.is_available() or torch.cuda.get_device_properties(0).multi_processor_count == 256
+
+    def probe(d, wg):
+        buf = ctypes.create_string_buffer(128)
+        rc = lib.rdn_conv_dgrad_wgrad_kernel_name(ctypes.byref(d), ctypes.byref(wg), buf, 128)
+        return (rc, buf.value.decode(), lib.rdn_conv_dgrad_wgrad_splits(ctypes.byref(d), ctypes.byref(wg)),
+                lib.rdn_conv_dgrad_wgrad_cols(ctypes.byref(d), ctypes.byref(wg)),
+                lib.rdn_conv_dgrad_wgrad_gate_rows(ctypes.byref(d), ctypes.byref(wg)))
+
+    def pair(key, nhw):
+        ck, nc, var = key
+        return _dw_pair(ck, nc, nhw, gated=var != "pregated", gout_c0=var if isinstance(var, int) else None)
+
+    assert len(_DW_SERVED) == 14
+    for key, (name, nh) in _DW_SERVED:
+        for nhw, splits in (((1, 8, 16), 8 * nh), ((2, 64, 64), {1: 64, 2: 128, 5: 240}[nh])):
+            rc, got, sp, cols, rows = probe(*pair(key, nhw))
+            assert (rc, got, cols) == (0, name, key[1] // nh), (key, nhw, rc, got, cols)
+            go = isinstance(key[2], int)
+            assert (rows > 0) == go and (not go or rows == sp), (key, nhw, rows, sp)
+            if cus256:
+                assert sp == splits, (key, nhw, sp)
+            else:
+                assert sp > 0 and sp % (8 * nh) == 0, (key, nhw, sp)
+        d, wg = pair(key, (1, 12, 16))   # ragged tile rows: not served
+        assert probe(d, wg) == (1, "", 0, 0, 0), key
+    for ck, nc in ((16, 96), (32, 112), (64, 128), (48, 48)):
+        assert probe(*_dw_pair(ck, nc, (2, 64, 64))) == (1, "", 0, 0, 0), (ck, nc)
+
+
 def test_state_dict_keys_and_shapes_match_oracle_spec():
     import vub_image_denoising_amd as vm
     from oracle.rdunet_ref import param_shapes

@@ -545,6 +545,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3_big_kernel(rdn_conv_desc d, 
             const f32x4 al = *(const f32x4*)(tab + COL_MAX + gc);
             const float pr[4] = {bf16lo(gpre[i][jn][0]), bf16hi(gpre[i][jn][0]), bf16lo(gpre[i][jn][1]),
                                  bf16hi(gpre[i][jn][1])};
+            // (rdn_prelu_bwd1's rule written out: through the helper the 253-255-VGPR
+            // gate-out kernels compile differently and gain scratch)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const bool pos = pr[e] > 0.f;

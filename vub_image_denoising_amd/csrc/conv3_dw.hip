@@ -64,6 +64,24 @@
 // up_0.conv (finishes up_0.conv_t: <48,32,h2>, gout_c0 = 32) and the level-1
 // conv_0s (finish down_0 / block_1_k.conv_3: <64,32>, gout_c0 = 0), whose separate
 // PReLU-backward passes (73 / 23 us each at B16) leave the compute queue.
+//
+// Schedules.  The 14 instantiations (dw_dispatch's table) run one of two tile loops,
+// chosen per shape <BN columns per block, CK dY channels> by DwCfg:
+//
+//   one barrier per tile (SB): dY and X halos double-buffered in LDS, one register set
+//     per role; every shape but the two below.  Within it:
+//       WSH    the W waves load and gate the dY halo ring, the D waves the tile interior
+//              (BSPLIT holds for all five): <32,16> <48,16> <80,16> <80,32> <48,32,h2,go>;
+//       DDMA   <32,64,h5,pregated>: the pre-gated dY halo by LDS-DMA into three buffers,
+//              the dgrad weight panel in registers (WREG), no gate in the kernel;
+//       else   the D waves load and gate the whole dY halo: <48,32> <64,32> <48,32,h2>
+//              <64,32,h2> <64,32,go> <32,64,h5>;
+//   two barriers per tile: one dY / X halo buffer in LDS, two register sets alternating
+//     in both roles (two X halos in flight in the W waves' registers, DW2): <64,16> and
+//     <32,32>, where the one-barrier form measured 1-3 us slower.
+//
+// The one-register-set W loops for shapes that are neither SB nor DW2 are gone: no
+// served shape took them, and a static_assert in DwCfg says so if a new shape would.
 #include "conv3_tile.h"
 #include "rdn_device.h"
 #include "rdn_launch.h"
@@ -102,6 +120,10 @@ __device__ unsigned long long g_dw_st[512 * 8 * 8];
 #define DW_NOW() __builtin_amdgcn_s_memtime()
 #endif
 
+// the pre-gated 64-channel dY halo (h5, no gate-out) arrives by LDS-DMA
+template <int CK, bool GO, bool GT>
+constexpr bool DW_DDMA = !GT && CK == 64 && !GO;
+
 template <int BN, int CK, bool GO = false, bool DDMA_ = false>
 struct DwCfg {
   static constexpr int KC = (9 * CK + 63) / 64 * 64;   // packed dgrad K (rdn_pack_weights, conv3_ws)
@@ -116,11 +138,10 @@ struct DwCfg {
   static_assert(!DDMA || (CK == 64 && !GO), "LDS-DMA dY halo: 8 units per pixel row");
   static constexpr int DROW = DDMA ? CK * 2 : c3::HaloRow<CK * 2>::V;   // dY halo row stride (b128 and tr16 conflict-free)
   static constexpr int XROW = c3::HaloRow<BN * 2>::V;   // X halo row stride
-  static constexpr bool D3 = WREG;                      // three dY halo buffers (h5)
-  static constexpr int D_PIECES = D3 ? ((HW_ * CK * 2 + 1023) / 1024 + 3) / 4 * 4 : (HW_ * CK * 2 + 1023) / 1024;
+  // (WREG shapes also run three dY halo buffers)
+  static constexpr int D_PIECES = WREG ? ((HW_ * CK * 2 + 1023) / 1024 + 3) / 4 * 4 : (HW_ * CK * 2 + 1023) / 1024;
   static constexpr int D_BYTES = DDMA ? D_PIECES * 1024 : (HW_ * DROW + 15) / 16 * 16;
   static constexpr int X_BYTES = (HW_ * XROW + 15) / 16 * 16;
-  static constexpr int CT_BYTES = 0;                    // dX leaves from the accumulators
   static constexpr bool SB_ = !((BN == 64 && CK == 16) || (BN == 32 && CK == 32));
   // W waves gate the dY halo ring (BSPLIT below) on the level-0 shapes: per launch at B16
   // (scripts/dw_kbench.py, profiles/r05_wsh_kbench_ab.txt) 32->16 57.0 -> 55.0 us, 80->32
@@ -132,9 +153,9 @@ struct DwCfg {
   static constexpr int RED_BYTES = 2 * (WSH ? 512 : 256) * 8 * 4;   // dalpha/dbias partial reduction (aliases)
   static constexpr int AL_BYTES = (CK * 4 + 15) / 16 * 16;   // gate slopes
   static constexpr int GAL_BYTES = GO ? BN * 4 : 0;           // gate-out: the finished layer's slopes
-  // W waves keep two X halos in flight in registers where the budget allows it
-  // (accumulators MTW x NTW x 4 + two X_IT sets within 256 VGPRs at 2 waves/SIMD);
-  // otherwise ONE register set and two X halo buffers in LDS
+  // two-barrier shapes: the W waves keep two X halos in flight in registers, which the
+  // budget must allow (accumulators MTW x NTW x 4 + two X_IT sets within 256 VGPRs at
+  // 2 waves/SIMD)
   static constexpr int X_IT = (HW_ * (BN / 8) + 255) / 256;
   static constexpr int NTW = (9 * BN / 16 + 3) / 4;
   static constexpr bool DW2 = (CK / 16) * NTW * 4 + 2 * X_IT * 4 <= 112;
@@ -143,32 +164,34 @@ struct DwCfg {
   // 32->16 59 -> 54 us, 80->32 135 -> 133, 64->32 36 -> 34; the 64->16 and 32->32
   // shapes ran 1-3 us slower and keep two barriers per tile)
   static constexpr bool SB = SB_;
-  static constexpr int DB = D3 ? 3 : SB ? 2 : 1;
-  static constexpr int BASE = W_BYTES + DB * D_BYTES + CT_BYTES + AL_BYTES + GAL_BYTES;
-  // X halo buffers in LDS: 2 for the LDS double buffer, 1 where it would not fit
-  // (96 columns were tried: <96,32> spills 128 B in the W loop, so they stay on the
+  static constexpr int DB = WREG ? 3 : SB ? 2 : 1;
+  static constexpr int BASE = W_BYTES + DB * D_BYTES + AL_BYTES + GAL_BYTES;
+  // X halo buffers in LDS: 2 for the one-barrier LDS double buffer, else 1.  The only
+  // two-barrier shapes are <64,16> and <32,32>, and both hold two X halos in registers:
+  // a shape that is neither has no W-wave schedule (the one-register-set forms for it are
+  // gone; 96 columns were tried: <96,32> spills 128 B in the W loop, so they stay on the
   // separate kernels)
-  static constexpr int XB = SB ? 2 : DW2 ? 1 : (BASE + 2 * X_BYTES <= LDS_MAX ? 2 : 1);
+  static_assert(SB || DW2, "two-barrier shape (only <64,16>, <32,32>) without two X halos in registers");
+  static constexpr int XB = SB ? 2 : 1;
   // 16 B per thread of a role: the padding units of the last halo load round store
   // here instead of skipping their store (a lane-divergent skip made hipcc wait
   // vmcnt(0) at the loop head, i.e. on the previous tile's dX stores)
   static constexpr int DUMP_BYTES = 256 * 16;
   static constexpr int LDS = BASE + XB * X_BYTES + DUMP_BYTES;
-  static constexpr bool FITS = LDS <= LDS_MAX && DB * D_BYTES + XB * X_BYTES + CT_BYTES >= RED_BYTES &&
+  static constexpr bool FITS = LDS <= LDS_MAX && DB * D_BYTES + XB * X_BYTES >= RED_BYTES &&
                               (!GO || W_BYTES >= 8 * BN * 4);   // gate-out partials in the dead panel
 };
 
 template <int BN, int CK, int NH, bool GO, bool GT>
 __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wgrad_desc wg, int tiles_x, int tiles_y,
                                                          int ntiles) {
-  using Cfg = DwCfg<BN, CK, GO, !GT && CK == 64 && !GO>;
+  using Cfg = DwCfg<BN, CK, GO, DW_DDMA<CK, GO, GT>>;
   constexpr bool DDMA = Cfg::DDMA;
   constexpr int VEC = 8;
   constexpr int KC = Cfg::KC, NSTEP = Cfg::NSTEP, WROW = Cfg::WROW, DROW = Cfg::DROW, XROW = Cfg::XROW;
   constexpr int NR = 256;                               // threads per role
   constexpr int MT = 2;                                 // dgrad: 2 x 16 pixels per D wave
   constexpr int NTL = BN / 16;                          // dgrad n-tiles
-  constexpr int NE = NTL;                               // epilogue operands per row
   constexpr int DU = CK / VEC, XU = BN / VEC;           // 16-B units per halo pixel
   constexpr int D_UNITS = HW_ * DU, X_UNITS = HW_ * XU;
   constexpr int D_IT = (D_UNITS + NR - 1) / NR, X_IT = (X_UNITS + NR - 1) / NR;
@@ -192,14 +215,13 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
   static_assert(NR % DU == 0, "fixed dY channel group per thread");
   static_assert(BN % 16 == 0 && CK % 16 == 0, "16-wide MFMA tiles");
   static_assert(Cfg::FITS, "LDS");
-  constexpr bool DW2 = Cfg::DW2;
   static_assert(Cfg::X_IT == X_IT && Cfg::NTW == NTW, "cfg");
 
   __shared__ __attribute__((aligned(16))) unsigned char lds[Cfg::LDS];
   unsigned char* const wl = lds;
   unsigned char* const dyh = lds + Cfg::W_BYTES;
   unsigned char* const xh = dyh + Cfg::DB * Cfg::D_BYTES;
-  float* const alds = (float*)(xh + Cfg::XB * Cfg::X_BYTES + Cfg::CT_BYTES);
+  float* const alds = (float*)(xh + Cfg::XB * Cfg::X_BYTES);
   unsigned char* const dump = lds + Cfg::LDS - Cfg::DUMP_BYTES;
   float* const galds = alds + Cfg::AL_BYTES / 4;        // (GO) slopes of the finished layer, this half's columns
   float* const gred = (float*)lds;                      // (GO) its partials, [D wave][2][BN] over the dead panel
@@ -384,14 +406,8 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
       const f32x4 a0 = *(const f32x4*)(alds + dcu * VEC), a1 = *(const f32x4*)(alds + dcu * VEC + 4);
       if (!live) {   // (block-uniform) no partials to count: the packed gate, ~half the VALU
 #pragma unroll
-        for (int it = 0; it < D_ITD; ++it) {
-          u32x4 o;
-          o[0] = rdn_gate2(lr[it][0], gr[it][0], a0[0], a0[1]);
-          o[1] = rdn_gate2(lr[it][1], gr[it][1], a0[2], a0[3]);
-          o[2] = rdn_gate2(lr[it][2], gr[it][2], a1[0], a1[1]);
-          o[3] = rdn_gate2(lr[it][3], gr[it][3], a1[2], a1[3]);
-          *(u32x4*)(uhp[it] < HW_ ? dyh + doff + llds[it] : dump + rt * 16) = o;
-        }
+        for (int it = 0; it < D_ITD; ++it)
+          *(u32x4*)(uhp[it] < HW_ ? dyh + doff + llds[it] : dump + rt * 16) = rdn_gate16(lr[it], gr[it], a0, a1);
         return;
       }
 #pragma unroll
@@ -401,6 +417,8 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
         Unit16<bf16>::unpack(gr[it], pr);
         const bool in = live && ((dint >> it) & 1u);   // a re-read past the range counts nothing
         unsigned char* const dst = uhp[it] < HW_ ? dyh + doff + llds[it] : dump + rt * 16;
+        // (rdn_prelu_bwd1's rule written out, as in the gate-out epilogue below: through the
+        // helper these two sites reorder the gated kernels' code, the W share's does not)
 #pragma unroll
         for (int q = 0; q < VEC; ++q) {
           const bool pos = pr[q] > 0.f;
@@ -411,7 +429,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
         *(u32x4*)dst = Unit16<bf16>::pack(dy);
       }
     };
-    auto load_epi = [&](int tt, u32x2 (&eo)[MT][NE]) {
+    auto load_epi = [&](int tt, u32x2 (&eo)[MT][NTL]) {
       int oy, ox, on;
       origin(tt, oy, ox, on);
       const int64_t opix0 = ((int64_t)on * H + oy) * W + ox;
@@ -471,7 +489,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
 #pragma unroll
         for (int jn = 0; jn < NTL; ++jn) asm volatile("" : "+v"(wreg[j][jn]));
     }
-    auto dgrad_tile = [&](int tt, const u32x2 (&eo)[MT][NE], int doff) {
+    auto dgrad_tile = [&](int tt, const u32x2 (&eo)[MT][NTL], int doff) {
       f32x4 acc[MT][NTL];
 #pragma unroll
       for (int i = 0; i < MT; ++i)
@@ -596,7 +614,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
     };
 
     u32x4 lA[D_ITD], gA[D_ITD], lB[D_ITD], gB[D_ITD];
-    u32x2 eC[MT][NE], eN[MT][NE];
+    u32x2 eC[MT][NTL], eN[MT][NTL];
     if constexpr (Cfg::SB) {
     // step k computes tile t from buffer k&1 while it gates tile t + per (issued one
     // step earlier) into buffer (k+1)&1 and issues tile t + 2 per: ONE barrier per
@@ -604,7 +622,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
     // register sets in flight measured no faster and spill the 80-column shape)
     if (t < t_hi) {
       if constexpr (DDMA) {
-        static_assert(Cfg::D3, "the LDS-DMA dY halo runs three buffers");
+        static_assert(Cfg::DB == 3, "the LDS-DMA dY halo runs three buffers");
         issue_d(t, 0);
         issue_d(min(t + per, t_last), Cfg::D_BYTES);
         load_epi(t, eC);
@@ -618,8 +636,8 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
       }
     }
     __syncthreads();   // weights + first halos
-    int dsel = 0;   // (D3) the dY buffer of tile t
-    auto step = [&](u32x4 (&lc)[D_ITD], u32x4 (&gc)[D_ITD], const u32x2 (&ec)[MT][NE], u32x2 (&en)[MT][NE],
+    int dsel = 0;   // (three dY buffers) the dY buffer of tile t
+    auto step = [&](u32x4 (&lc)[D_ITD], u32x4 (&gc)[D_ITD], const u32x2 (&ec)[MT][NTL], u32x2 (&en)[MT][NTL],
                     int cur) -> bool {
       const int t1 = t + per;
       if constexpr (DDMA) {   // tile t + 2 per's dY halo DMA'd after this tile's epilogue
@@ -671,7 +689,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
     }
     __syncthreads();   // weights + first halos
     auto step = [&](u32x4 (&lc)[D_ITD], u32x4 (&gc)[D_ITD], u32x4 (&ln)[D_ITD], u32x4 (&gn)[D_ITD],
-                    const u32x2 (&ec)[MT][NE], u32x2 (&en)[MT][NE]) -> bool {
+                    const u32x2 (&ec)[MT][NTL], u32x2 (&en)[MT][NTL]) -> bool {
       const int t1 = t + per;
       load(min(t + 2 * per, t_last), ln, gn);
       load_epi(min(t1, t_last), en);
@@ -721,9 +739,9 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
     const int xupp = (wg.b_pl && xc0 % wg.b_ps == 0 && XU % (wg.b_ps / VEC) == 0) ? (int)(wg.b_ps / VEC) : XU;
     // per unit: global offset and LDS offset (-1: padding unit; its halo pixel is
     // llds / XROW, so no third array)
-    // (XREC: the two index arrays recomputed per use instead of held -- tried for the W
-    // share of the widest shape, it spilled more)
-    constexpr bool XREC = false;
+    // (the two index arrays recomputed per use instead of held -- tried for the W share
+    // of the widest shape -- spilled more; the lambda stays: the same arithmetic written
+    // into the loop below orders the prologue's address math differently)
     auto xunit = [&](int it, int& rel, int& ll) {
       const int u = rt + it * NR;
       const int pln = u / (HW_ * xupp), rem = u - pln * (HW_ * xupp);
@@ -733,29 +751,9 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
       rel = (hy * W + hx) * (int)wg.b_ps + rdn_coff32(xc0 + cu * VEC, (int)wg.b_ps, (int)wg.b_pl);
       ll = ok ? hq * XROW + cu * 16 : -1;
     };
-    int lrel_[XREC ? 1 : X_IT], llds_[XREC ? 1 : X_IT];
-    if constexpr (!XREC) {
+    int xrel[X_IT], xlds[X_IT];
 #pragma unroll
-      for (int it = 0; it < X_IT; ++it) xunit(it, lrel_[it], llds_[it]);
-    }
-    auto xrel = [&](int it) {
-      if constexpr (XREC) {
-        int rel, ll;
-        xunit(it, rel, ll);
-        return rel;
-      } else {
-        return lrel_[it];
-      }
-    };
-    auto xlds = [&](int it) {
-      if constexpr (XREC) {
-        int rel, ll;
-        xunit(it, rel, ll);
-        return ll;
-      } else {
-        return llds_[it];
-      }
-    };
+    for (int it = 0; it < X_IT; ++it) xunit(it, xrel[it], xlds[it]);
     auto load = [&](int tt, u32x4 (&lr)[X_IT]) {
       int oy, ox, on;
       origin(tt, oy, ox, on);
@@ -763,14 +761,14 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
       const __amdgpu_buffer_rsrc_t rx = rdn_rsrc(XS + hpix0 * wg.b_ps);
 #pragma unroll
       for (int it = 0; it < X_IT; ++it) {
-        const int ll = xlds(it);
-        lr[it] = rdn_ld16(rx, in_img(ll < 0 ? HW_ : ll / XROW, oy, ox), xrel(it) * 2);
+        const int ll = xlds[it];
+        lr[it] = rdn_ld16(rx, in_img(ll < 0 ? HW_ : ll / XROW, oy, ox), xrel[it] * 2);
       }
     };
     auto store = [&](const u32x4 (&lr)[X_IT], int xoff) {
 #pragma unroll
       for (int it = 0; it < X_IT; ++it) {
-        const int ll = xlds(it);
+        const int ll = xlds[it];
         *(u32x4*)(ll >= 0 ? xh + xoff + ll : dump + rt * 16) = lr[it];
       }
     };
@@ -821,24 +819,14 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
       } else {
         const f32x4 a0 = *(const f32x4*)(alds + wdcu * VEC), a1 = *(const f32x4*)(alds + wdcu * VEC + 4);
         if (BSPLIT || !live) {   // (block-uniform) the packed gate, no partials
-          u32x4 o;
-          o[0] = rdn_gate2(lr[0], gr[0], a0[0], a0[1]);
-          o[1] = rdn_gate2(lr[1], gr[1], a0[2], a0[3]);
-          o[2] = rdn_gate2(lr[2], gr[2], a1[0], a1[1]);
-          o[3] = rdn_gate2(lr[3], gr[3], a1[2], a1[3]);
-          *(u32x4*)dst = o;
+          *(u32x4*)dst = rdn_gate16(lr, gr, a0, a1);
           return;
         }
         float dy[VEC], pr[VEC];
         Unit16<bf16>::unpack(lr, dy);
         Unit16<bf16>::unpack(gr, pr);
 #pragma unroll
-        for (int q = 0; q < VEC; ++q) {
-          const bool pos = pr[q] > 0.f;
-          if (wint && !pos) wsa[q] += pr[q] * dy[q];
-          dy[q] = pos ? dy[q] : (q < 4 ? a0[q] : a1[q - 4]) * dy[q];
-          if (wint) wsb[q] += dy[q];
-        }
+        for (int q = 0; q < VEC; ++q) rdn_prelu_bwd1(dy[q], pr[q], q < 4 ? a0[q] : a1[q - 4], wint, wsa[q], wsb[q]);
         *(u32x4*)dst = Unit16<bf16>::pack(dy);
       }
     };
@@ -934,7 +922,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
 #ifdef DW_STAMPS
         const unsigned long long s2 = DW_NOW();
 #endif
-        wgrad_tile(cur * Cfg::X_BYTES, (Cfg::D3 ? k % 3 : cur) * Cfg::D_BYTES);
+        wgrad_tile(cur * Cfg::X_BYTES, (Cfg::DB == 3 ? k % 3 : cur) * Cfg::D_BYTES);
 #ifdef DW_STAMPS
         const unsigned long long s3 = DW_NOW();
 #endif
@@ -947,7 +935,8 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
       }
     }
     } else {
-    if constexpr (DW2) {   // two tiles in flight: register sets alternate
+    {   // two barriers per tile, two tiles in flight: register sets alternate
+      static_assert(Cfg::DW2, "the two-barrier W waves hold two X halos in registers (DwCfg::XB)");
       u32x4 lA[X_IT], lB[X_IT];
       if (t < t_hi) {
         load(t, lA);
@@ -966,44 +955,7 @@ __global__ __launch_bounds__(NT, 1) void conv3_dw_kernel(rdn_conv_desc d, rdn_wg
       };
       if (t < t_hi)
         while (step(lA, lB) && step(lB, lA)) {}
-    } else if constexpr (Cfg::XB == 2) {
-      // one register set, two X halo buffers: at the top of step k the set holds tile
-      // k+1 (issued a whole step earlier); it goes to buffer (k+1)&1 -- free since
-      // step k-1's MFMAs -- and takes tile k+2 while tile k computes from buffer k&1
-      u32x4 lA[X_IT];
-      if (t < t_hi) {
-        load(t, lA);
-        store(lA, 0);
-        load(min(t + per, t_last), lA);
-      }
-      __syncthreads();   // weights + first halos
-      int k = 0;
-      while (t < t_hi) {
-        store(lA, ((k + 1) & 1) * Cfg::X_BYTES);   // tile t + per (a re-read past the range)
-        load(min(t + 2 * per, t_last), lA);
-        wgrad_tile((k & 1) * Cfg::X_BYTES, 0);
-        __syncthreads();   // halos of t consumed; X of t + per visible
-        __syncthreads();   // (the D waves' dY halo of t + per)
-        t += per;
-        ++k;
-      }
-    } else {   // one tile of X in flight (96 columns: neither budget holds two)
-      u32x4 lA[X_IT];
-      if (t < t_hi) {
-        load(t, lA);
-        store(lA, 0);
-      }
-      __syncthreads();   // weights + first halos
-      while (t < t_hi) {
-        load(min(t + per, t_last), lA);
-        wgrad_tile(0, 0);
-        __syncthreads();   // halos of t consumed
-        store(lA, 0);
-        __syncthreads();   // halos of t1 visible
-        t += per;
-      }
     }
-
     }
 
     // this block's split of the weight gradient (zero slab for a block without tiles);
@@ -1110,8 +1062,7 @@ int dw_nh(const rdn_conv_desc* d) {
 // gate-out (d->gout) on this pair: the instantiated shapes (up_0.conv: 96 columns in
 // halves; the level-1 conv_0: 64 columns), whole 4-channel units, 8-byte aligned
 // operands, 32-bit per-tile offsets
-bool dw_gout_ok(const rdn_conv_desc* d, const rdn_wgrad_desc* wg) {
-  const int nh = dw_nh(d);
+bool dw_gout_ok(const rdn_conv_desc* d, const rdn_wgrad_desc* wg, int nh) {
   if (d->cin != 32 || !((d->ncols == 96 && nh == 2) || (d->ncols == 64 && nh == 1))) return false;
   if (!d->gout_pre || !d->gout_alpha || !d->gout_part || !wg->part || (d->flags & RDN_EPI_RESID)) return false;
   if (d->gout_c0 < 0 || d->gout_c0 >= d->ncols || d->gout_c0 % 4 || d->gout_ps % 4 || d->gout_pre_ps % 4) return false;
@@ -1120,9 +1071,10 @@ bool dw_gout_ok(const rdn_conv_desc* d, const rdn_wgrad_desc* wg) {
   return (int64_t)TH * d->w * d->gout_ps < (1ll << 30) && (int64_t)TH * d->w * d->gout_pre_ps < (1ll << 30);
 }
 
-// the pair this kernel serves (else 1 = run the separate dgrad / wgrad launches)
-bool dw_serves(const rdn_conv_desc* d, const rdn_wgrad_desc* wg) {
-  if (!dw_enabled() || !d || !wg) return false;
+// the pair this kernel serves (else 1 = run the separate dgrad / wgrad launches);
+// nh = dw_nh(d)
+bool dw_serves(const rdn_conv_desc* d, const rdn_wgrad_desc* wg, int nh) {
+  if (!dw_enabled()) return false;
   if (d->dtype != RDN_BF16 || wg->dtype != RDN_BF16 || d->gather != RDN_G_CONV3 || wg->gather != RDN_G_CONV3) return false;
   if (d->bn || d->bm) return false;
   // gated (the loaders apply the PReLU backward, dalpha/dbias partials in wg->part) or,
@@ -1130,11 +1082,10 @@ bool dw_serves(const rdn_conv_desc* d, const rdn_wgrad_desc* wg) {
   // by a gate-out finisher or the PReLU-backward pass, which also count the partials)
   const bool gated = d->gate && wg->a_gate && d->gate_alpha;
   if (!gated && (d->gate || wg->a_gate || wg->part || !(d->cin == 64 && d->ncols == 160))) return false;
-  if (d->gout && !dw_gout_ok(d, wg)) return false;
+  if (d->gout && !dw_gout_ok(d, wg, nh)) return false;
   if (d->flags & ~(RDN_EPI_RESID | RDN_EPI_ACCUM | (d->gout ? RDN_EPI_GOUT_KEEP : 0))) return false;
   if ((d->flags & RDN_EPI_RESID) && (d->flags & RDN_EPI_ACCUM)) return false;
   if (d->h % TH || d->w % TW || d->n != wg->n || d->h != wg->h || d->w != wg->w) return false;
-  const int nh = dw_nh(d);
   if (d->cin != 16 && d->cin != 32 && !(d->cin == 64 && nh == 5)) return false;
   if (d->ncols != d->cout || d->ncols % 16 || d->ncols < 32 || d->ncols / nh > 80 || wg->ndim != d->ncols) return false;
   if (wg->mdim > d->cin || wg->mdim <= 0 || !rdn_aligned(wg->b_ps, wg->b_c0, wg->b)) return false;
@@ -1163,7 +1114,7 @@ bool dw_serves(const rdn_conv_desc* d, const rdn_wgrad_desc* wg) {
 
 template <int BN, int CK, int NH = 1, bool GO = false, bool GT = true>
 int launch_dw(const rdn_conv_desc* d, const rdn_wgrad_desc* wg, hipStream_t st) {
-  if constexpr (!DwCfg<BN, CK, GO, !GT && CK == 64 && !GO>::FITS) {
+  if constexpr (!DwCfg<BN, CK, GO, DW_DDMA<CK, GO, GT>>::FITS) {
     return 1;
   } else {
     const int tiles_x = d->w / TW, tiles_y = d->h / TH;
@@ -1183,42 +1134,49 @@ int launch_dw(const rdn_conv_desc* d, const rdn_wgrad_desc* wg, hipStream_t st) 
   }
 }
 
-template <int CK>
-int dw_bn(const rdn_conv_desc* d, const rdn_wgrad_desc* wg, hipStream_t st) {
-  if constexpr (CK == 64) {   // (dw_serves: the level-1 conv_3, 160 input channels in five parts)
-    if (!d->gout && dw_nh(d) == 5 && d->ncols == 160)
-      return d->gate ? launch_dw<32, 64, 5>(d, wg, st) : launch_dw<32, 64, 5, false, false>(d, wg, st);
-    return 1;
-  } else {
-  if (d->gout) {   // (dw_gout_ok: these two shapes only)
-    if constexpr (CK == 32) {
-      if (d->ncols == 96) return launch_dw<48, 32, 2, true>(d, wg, st);
-      if (d->ncols == 64) return launch_dw<64, 32, 1, true>(d, wg, st);
-    }
-    return 1;
-  }
-  if constexpr (CK == 32) {
-    if (dw_nh(d) == 2) {
-      switch (d->ncols) {
-        case 96: return launch_dw<48, 32, 2>(d, wg, st);
-        case 128: return launch_dw<64, 32, 2>(d, wg, st);
-      }
-      return 1;
-    }
-  }
-  switch (d->ncols) {
-    case 32: return launch_dw<32, CK>(d, wg, st);
-    case 48: return launch_dw<48, CK>(d, wg, st);
-    case 64: return launch_dw<64, CK>(d, wg, st);
-    case 80: return launch_dw<80, CK>(d, wg, st);
-  }
+// The served set, one row per instantiation: (dY channels = d->cin, input channels =
+// d->ncols, column parts nh, gate-out, dY gated in the loaders) -> the kernel of
+// ncols / nh columns per block.  dw_serves admits nothing else: gate-out only on the two
+// shapes of dw_gout_ok, an ungated (pre-gated) dY only on the five-part level-1 conv_3.
+// 0 = launched (or, probing, named), 1 = not served; *nh_out = the pair's column parts.
+int dw_dispatch(const rdn_conv_desc* d, const rdn_wgrad_desc* wg, hipStream_t st, int* nh_out = nullptr) {
+  if (!d || !wg) return 1;
+  const int nh = dw_nh(d);
+  if (nh_out) *nh_out = nh;
+  if (!dw_serves(d, wg, nh)) return 1;
+  const bool go = d->gout != nullptr, gt = d->gate != nullptr;
+#define DW_ROW(CK_, NCOLS_, NH_, GO_, GT_)                                        \
+  if (d->cin == CK_ && d->ncols == NCOLS_ && nh == NH_ && go == GO_ && gt == GT_) \
+    return launch_dw<NCOLS_ / NH_, CK_, NH_, GO_, GT_>(d, wg, st)
+  //     dY  in  nh  gate-out  gated
+  DW_ROW(16, 32, 1, false, true);    // level 0
+  DW_ROW(16, 48, 1, false, true);
+  DW_ROW(16, 64, 1, false, true);
+  DW_ROW(16, 80, 1, false, true);
+  DW_ROW(32, 32, 1, false, true);
+  DW_ROW(32, 48, 1, false, true);
+  DW_ROW(32, 64, 1, false, true);    // (and the level-1 conv_0 without gate-out)
+  DW_ROW(32, 80, 1, false, true);
+  DW_ROW(32, 96, 2, false, true);    // level-1 conv_1, up_0.conv: halves
+  DW_ROW(32, 128, 2, false, true);   // level-1 conv_2: halves
+  DW_ROW(32, 96, 2, true, true);     // up_0.conv finishing up_0.conv_t
+  DW_ROW(32, 64, 1, true, true);     // level-1 conv_0 finishing down_0 / block_1_k.conv_3
+  DW_ROW(64, 160, 5, false, true);   // level-1 conv_3: five 32-channel parts
+  DW_ROW(64, 160, 5, false, false);  //   its dY pre-gated (LDS-DMA halo)
+#undef DW_ROW
   return 1;
-  }
 }
 
-int dw_dispatch(const rdn_conv_desc* d, const rdn_wgrad_desc* wg, hipStream_t st) {
-  if (!dw_serves(d, wg)) return 1;
-  return d->cin == 64 ? dw_bn<64>(d, wg, st) : d->cin == 32 ? dw_bn<32>(d, wg, st) : dw_bn<16>(d, wg, st);
+// splits of the pair (0 = not served) and its column parts, without launching: the
+// dispatch runs with an 8-byte probe buffer, so the row's launcher only names itself
+int dw_probe(const rdn_conv_desc* d, const rdn_wgrad_desc* wg, int* nh) {
+  char buf[8];
+  rdn_probe_buf = buf;
+  rdn_probe_len = (int)sizeof(buf);
+  const int rc = dw_dispatch(d, wg, nullptr, nh);   // instantiation exists for this shape?
+  rdn_probe_buf = nullptr;
+  if (rc != 0) return 0;
+  return dw_grid(d->n * (d->h / TH) * (d->w / TW), *nh);
 }
 
 }  // namespace
@@ -1233,21 +1191,15 @@ extern "C" int rdn_conv_dgrad_wgrad(const rdn_conv_desc* dgrad, const rdn_wgrad_
 
 // split count (= persistent grid) the fused kernel writes for this pair, 0 if not served
 extern "C" int rdn_conv_dgrad_wgrad_splits(const rdn_conv_desc* dgrad, const rdn_wgrad_desc* wgrad) {
-  if (!dw_serves(dgrad, wgrad)) return 0;
-  char buf[8];
-  rdn_probe_buf = buf;
-  rdn_probe_len = (int)sizeof(buf);
-  const int rc = dw_dispatch(dgrad, wgrad, nullptr);   // instantiation exists for this shape?
-  rdn_probe_buf = nullptr;
-  if (rc != 0) return 0;
-  return dw_grid(dgrad->n * (dgrad->h / TH) * (dgrad->w / TW), dw_nh(dgrad));
+  int nh;
+  return dw_probe(dgrad, wgrad, &nh);
 }
 
 // input channels per weight-gradient slab (= wgrad->ndim, or ndim / 2 with column
 // halves: the slabs of half h are [h*splits/2, (h+1)*splits/2)), 0 if not served
 extern "C" int rdn_conv_dgrad_wgrad_cols(const rdn_conv_desc* dgrad, const rdn_wgrad_desc* wgrad) {
-  if (!rdn_conv_dgrad_wgrad_splits(dgrad, wgrad)) return 0;
-  return dgrad->ncols / dw_nh(dgrad);
+  int nh;
+  return dw_probe(dgrad, wgrad, &nh) ? dgrad->ncols / nh : 0;
 }
 
 // partial rows the gate-out epilogue writes for the finished layer (one per block of
@@ -1267,7 +1219,6 @@ extern "C" int rdn_conv_dgrad_wgrad_kernel_name(const rdn_conv_desc* dgrad, cons
                                                 int32_t len) {
   if (!buf || len < 1) { rdn_set_error("rdn_conv_dgrad_wgrad_kernel_name: no buffer"); return RDN_E_ARG; }
   buf[0] = 0;
-  if (!dgrad || !wgrad || !dw_serves(dgrad, wgrad)) return 1;
   rdn_probe_buf = buf;
   rdn_probe_len = len;
   const int rc = dw_dispatch(dgrad, wgrad, nullptr);

@@ -415,12 +415,7 @@ __global__ __launch_bounds__(NT, (BN >= 64 ? 1 : 2)) void conv3_halo_kernel(rdn_
       float pr[VEC];
       Unit16<T>::unpack(*(const u32x4*)((const T*)d.gout_pre + opix * d.gout_pre_ps + gc), pr);
 #pragma unroll
-      for (int q = 0; q < VEC; ++q) {
-        const bool pos = pr[q] > 0.f;
-        if (!pos) gsa[q] += pr[q] * v[q];
-        v[q] = pos ? v[q] : oalpha[q] * v[q];
-        gsb[q] += v[q];
-      }
+      for (int q = 0; q < VEC; ++q) rdn_prelu_bwd1(v[q], pr[q], oalpha[q], true, gsa[q], gsb[q]);
       *(u32x4*)((T*)d.gout + opix * d.gout_ps + gc) = Unit16<T>::pack(v);
       continue;
     }

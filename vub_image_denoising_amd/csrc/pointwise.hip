@@ -86,6 +86,8 @@ static int grid_for(int64_t n, int per_block, int cap = 8192) {
 // dyp = dy * (pre > 0 ? 1 : a);  dalpha += sum_{pre<=0} pre*dy;  dbias += sum dyp
 // (aten prelu backward: mask = input > 0, Activation.cpp; conv grad_bias = sum
 // over N,H,W of grad_output).  Thread = 16-byte channel group of one pixel.
+// (The element rule is rdn_prelu_bwd1's, written out in both loops with the channel mask:
+// through the helper the masked form compiles to different code.)
 template <typename T>
 // (<= 64 VGPRs: one wave per SIMD still fits beside a two-wave weight-gradient block of
 // the side stream -- 2 x 218 of 512 -- so the pass is not confined to the CUs the

@@ -139,6 +139,33 @@ __device__ __forceinline__ unsigned rdn_gate2(unsigned dy, unsigned pre, float a
   const unsigned g = rdn_cvt2(lo, hi);
   return (g & m) | (dy & ~m);
 }
+// the same over a 16-byte unit of 8 channels with slopes a0 (channels 0-3), a1 (4-7)
+__device__ __forceinline__ u32x4 rdn_gate16(const u32x4& dy, const u32x4& pre, const f32x4& a0, const f32x4& a1) {
+  u32x4 o;
+  o[0] = rdn_gate2(dy[0], pre[0], a0[0], a0[1]);
+  o[1] = rdn_gate2(dy[1], pre[1], a0[2], a0[3]);
+  o[2] = rdn_gate2(dy[2], pre[2], a1[0], a1[1]);
+  o[3] = rdn_gate2(dy[3], pre[3], a1[2], a1[3]);
+  return o;
+}
+// PReLU backward of one element in fp32, the rule every kernel that gates dY shares (they
+// must agree bit for bit: a layer's gradients may not depend on the kernel it was routed
+// to): dY becomes dYpre = pre > 0 ? dY : alpha * dY in place and, where `count`, the
+// element's dalpha term pre * dY (slope branch only) is added to `dalpha` and dYpre, before
+// its rounding to the storage type, to `dbias`; the second form is for callers that sum
+// dbias themselves.  (Operands by reference: passed by value the callers' assembly changed.)
+__device__ __forceinline__ void rdn_prelu_bwd1(float& dy, const float& pre, const float& alpha, bool count,
+                                               float& dalpha, float& dbias) {
+  const bool pos = pre > 0.f;
+  if (count && !pos) dalpha += pre * dy;
+  dy = pos ? dy : alpha * dy;
+  if (count) dbias += dy;
+}
+__device__ __forceinline__ void rdn_prelu_bwd1(float& dy, const float& pre, const float& alpha, bool count,
+                                               float& dalpha) {
+  float unused = 0.f;
+  rdn_prelu_bwd1(dy, pre, alpha, count, dalpha, unused);
+}
 
 // Fast unsigned division by a runtime-invariant divisor (n < 2^31).
 struct FastDiv {

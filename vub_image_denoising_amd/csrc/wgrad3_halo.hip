@@ -137,11 +137,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad3_halo_kernel(rdn_wgrad_desc d, in
           Unit16<T>::unpack(v, dy);
           Unit16<T>::unpack(greg[it], pr);
 #pragma unroll
-          for (int q = 0; q < VEC; ++q) {
-            const bool pos = pr[q] > 0.f;
-            if (!pos) sa[q] += pr[q] * dy[q];
-            dy[q] = pos ? dy[q] : galpha[q] * dy[q];
-          }
+          for (int q = 0; q < VEC; ++q) rdn_prelu_bwd1(dy[q], pr[q], galpha[q], true, sa[q]);
           v = Unit16<T>::pack(dy);
           if (do_part) {  // dbias sums dYpre before its rounding to T, as rdn_prelu_bwd does
 #pragma unroll
@@ -416,11 +412,7 @@ __global__ __launch_bounds__(NT, (BM * CK > 2560 ? 1 : 2)) void wgrad3_rows_kern
         Unit16<bf16>::unpack(v, dy);
         Unit16<bf16>::unpack(greg[it], pr);
 #pragma unroll
-        for (int q = 0; q < VEC; ++q) {
-          const bool pos = pr[q] > 0.f;
-          if (!pos) sa[q] += pr[q] * dy[q];
-          dy[q] = pos ? dy[q] : galpha[q] * dy[q];
-        }
+        for (int q = 0; q < VEC; ++q) rdn_prelu_bwd1(dy[q], pr[q], galpha[q], true, sa[q]);
         v = Unit16<bf16>::pack(dy);
         if (do_part) {  // dbias sums dYpre before its rounding, as rdn_prelu_bwd does
 #pragma unroll

@@ -310,6 +310,24 @@ int rdn_charbonnier_fwd(const float* pred, const float* target, int64_t count, f
 int rdn_charbonnier_bwd(const float* pred, const float* target, int64_t count, float eps,
                         float wc, float wm, const float* gout, float* dpred, void* stream);
 
+/* SSIM term of combined_loss (diffusion_RDUnet.py:60-65): pytorch_msssim.ssim (v1.0.0;
+   gaussian 11, sigma 1.5, valid, size_average) of fp32 NCHW x, y.  ws:
+   rdn_ssim_workspace_size bytes (one fp32 partial sum per block; 0 for a shape the
+   launchers refuse).  coef != NULL: the forward also keeps dS/dm1, dS/dq, dS/dp (the
+   SSIM map's derivatives by the filtered x, x^2 and xy) for rdn_ssim_bwd.  Valid:
+   h, w >= 11, n*c in [1, 65535], at most 2^23 tiles of 32x32; anything else returns
+   RDN_E_ARG before any launch, the message naming the argument.  No atomics: the same
+   call gives the same bits. */
+int64_t rdn_ssim_workspace_size(int32_t n, int32_t c, int32_t h, int32_t w);
+int rdn_ssim_fwd(const float* x, const float* y, int32_t n, int32_t c, int32_t h, int32_t w,
+                 float data_range, float* coef /* NULL, or [3][n][c][h-10][w-10] */,
+                 float* ws, float* out /* out[0] = mean SSIM */, void* stream);
+/* dx (+)= gout[0] * weight * d(mean SSIM)/dx ; accumulate != 0 adds onto dx.  Every
+   element of dx is written. */
+int rdn_ssim_bwd(const float* x, const float* y, const float* coef, int32_t n, int32_t c,
+                 int32_t h, int32_t w, float weight, const float* gout, float* dx,
+                 int32_t accumulate, void* stream);
+
 /* out[0] = sqrt(sum g^2) over a flat fp32 buffer; out[1] = min(max_norm/(out[0]+1e-6), 1) */
 int rdn_sqnorm(const float* g, int64_t count, float max_norm, float* ws, float* out, void* stream);
 /* the same for pre_scale*g without scaling g (pre_scale > 0: the data-parallel 1/world

@@ -86,7 +86,7 @@ def _draw_t(batch_size, timesteps, distribution_choice, dev):
     return torch.randint(0, timesteps + 1, (batch_size,), device=dev).float()
 
 
-def _forward_loss(model, clean_images, noisy_images, distribution_choice, t):
+def _forward_loss(model, clean_images, noisy_images, distribution_choice, t, loss_weights=None):
     B = clean_images.size(0)
     T = model.timesteps
     if t is None:
@@ -95,19 +95,21 @@ def _forward_loss(model, clean_images, noisy_images, distribution_choice, t):
     interpolated = Fn.interpolate(clean_images, noisy_images, t_normalized)            # :99-100
     t_tensor = t_normalized.view(B, 1, 1, 1).expand(-1, 1, clean_images.size(2), clean_images.size(3))  # :93
     denoised = model.unet(interpolated, t_tensor)                                      # :106
-    return combined_loss(denoised, clean_images)                                       # :109
+    return combined_loss(denoised, clean_images, *Fn.loss_weights_or_default(loss_weights))   # :109
 
 
 def train_step_device(model, clean_images, noisy_images, optimizer, distribution_choice='uniform',
-                      clip_value=0.1, t=None, zero_grad=True, clip=True):
+                      clip_value=0.1, t=None, zero_grad=True, clip=True, loss_weights=None):
     """The body of train_step_checkpointed without the host sync: returns the
     loss as a device tensor.  ``t`` (integer steps, [B]) overrides the draw.
     ``zero_grad=False, clip=False`` accumulates into the existing gradients
-    (the fixed accumulation mode of run_epochs)."""
+    (the fixed accumulation mode of run_epochs).  ``loss_weights``: the
+    ``(mse, charbonnier, ssim)`` weights of ``combined_loss``, None for the
+    reference's (0, 1, 0)."""
     model.train()
     if zero_grad:
         optimizer.zero_grad()
-    loss = _forward_loss(model, clean_images, noisy_images, distribution_choice, t)
+    loss = _forward_loss(model, clean_images, noisy_images, distribution_choice, t, loss_weights)
     # data-parallel: the clip right after the backward also applies the 1/world
     # average of the all-reduced gradient (one pass instead of two, ddp.py)
     # -- only when the gradients are this backward's alone (zero_grad): accumulated
@@ -136,7 +138,8 @@ def train_step_device(model, clean_images, noisy_images, optimizer, distribution
     return loss
 
 
-def forward_step_device(model, clean_images, noisy_images, distribution_choice='uniform', t=None, need_loss=True):
+def forward_step_device(model, clean_images, noisy_images, distribution_choice='uniform', t=None, need_loss=True,
+                        loss_weights=None):
     """A train step whose gradient the reference throws away (diffusion_RDUnet.py:78:
     the next step's zero_grad): the same timestep draw (so the RNG streams stay the
     reference's) and, when the loss is logged, the same forward + loss without
@@ -147,32 +150,34 @@ def forward_step_device(model, clean_images, noisy_images, distribution_choice='
         return None
     model.train()
     with torch.no_grad():
-        return _forward_loss(model, clean_images, noisy_images, distribution_choice, t)
+        return _forward_loss(model, clean_images, noisy_images, distribution_choice, t, loss_weights)
 
 
 def train_step_checkpointed(model, clean_images, noisy_images, optimizer, accumulation_steps,
-                            distribution_choice='uniform', clip_value=0.1, *, t=None):
+                            distribution_choice='uniform', clip_value=0.1, *, t=None, loss_weights=None):
     """diffusion_RDUnet.py:76-115 (returns ``loss.item()`` like the reference).
     ``main_diffusion_RDUnet.py``'s variant has no ``distribution_choice``; passing
     the clip value positionally there works the same (a float is taken as the
     clip value)."""
     if isinstance(distribution_choice, (int, float)) and not isinstance(distribution_choice, bool):
         clip_value, distribution_choice = float(distribution_choice), 'uniform'
-    loss = train_step_device(model, clean_images, noisy_images, optimizer, distribution_choice, clip_value, t=t)
+    loss = train_step_device(model, clean_images, noisy_images, optimizer, distribution_choice, clip_value, t=t,
+                             loss_weights=loss_weights)
     return loss.item()
 
 
 def train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir,
                              distribution_choice='uniform', num_epochs=10, start_epoch=0, accumulation_steps=4,
-                             clip_value=1.0, log_every=1, accumulation='reference'):
+                             clip_value=1.0, log_every=1, accumulation='reference', loss_weights=None):
     """diffusion_RDUnet.py:117-178: epochs of train steps with the reference's
     every-``accumulation_steps`` optimizer step, one-batch improved_sampling
     validation, scheduler step and a checkpoint dict per epoch.  ``log_every``
     > 1 rate-limits the per-batch ``loss.item()`` host sync; ``accumulation``
-    selects the reference's update rule or the fixed one (see run_epochs)."""
+    selects the reference's update rule or the fixed one (see run_epochs);
+    ``loss_weights`` the loss mix of the train steps and the validation loss."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir, distribution_choice,
                num_epochs, start_epoch, accumulation_steps, clip_value, log_every,
-               sample=lambda m, x: m.improved_sampling(x), accumulation=accumulation)
+               sample=lambda m, x: m.improved_sampling(x), accumulation=accumulation, loss_weights=loss_weights)
 
 
 ACCUMULATION_MODES = ("reference", "fixed")
@@ -180,7 +185,7 @@ ACCUMULATION_MODES = ("reference", "fixed")
 
 def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir, distribution_choice,
                num_epochs, start_epoch, accumulation_steps, clip_value, log_every, sample, accumulation='reference',
-               skip_discarded=True):
+               skip_discarded=True, loss_weights=None):
     """The epoch loop shared by the three reference trainers (diffusion_RDUnet.py:117-178,
     main_diffusion_RDUnet.py:275-336, diffusion_RDUnet_direct.py:266-327); they
     differ only in the validation sampler and the checkpoint directory.
@@ -195,7 +200,9 @@ def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, ou
     accumulation='fixed' accumulates the gradients of ``accumulation_steps``
     batches and clips + steps once (the rule of UNet/RDUNet_model.py:201-215).
     ``skip_discarded=False`` runs the discarded backward passes anyway (the
-    reference's literal work; tests compare the two bit for bit)."""
+    reference's literal work; tests compare the two bit for bit).
+    ``loss_weights``: the ``(mse, charbonnier, ssim)`` weights of the train and
+    validation loss, None for the reference's (0, 1, 0)."""
     if accumulation not in ACCUMULATION_MODES:
         raise ValueError(f"accumulation must be one of {ACCUMULATION_MODES}, got {accumulation!r}")
     dev = next(model.parameters()).device
@@ -209,15 +216,15 @@ def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, ou
             log_now = batch_idx % log_every == 0
             if accumulation == 'fixed':
                 loss_t = train_step_device(model, clean_images, noisy_images, optimizer, distribution_choice,
-                                           clip_value, zero_grad=False, clip=False)
+                                           clip_value, zero_grad=False, clip=False, loss_weights=loss_weights)
                 if step_now:
                     Fn.clip_grad_norm_(model.parameters(), clip_value)
             elif step_now or not skip_discarded:
                 loss_t = train_step_device(model, clean_images, noisy_images, optimizer, distribution_choice,
-                                           clip_value)
+                                           clip_value, loss_weights=loss_weights)
             else:
                 loss_t = forward_step_device(model, clean_images, noisy_images, distribution_choice,
-                                             need_loss=log_now)
+                                             need_loss=log_now, loss_weights=loss_weights)
             if step_now:
                 optimizer.step()
                 optimizer.zero_grad()
@@ -233,7 +240,8 @@ def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, ou
                 val_noisy_images, val_clean_images = next(iter(val_loader))
                 val_noisy_images, val_clean_images = val_noisy_images.to(dev), val_clean_images.to(dev)
                 denoised_images = sample(model, val_noisy_images)
-                validation_loss = combined_loss(denoised_images, val_clean_images).item()
+                validation_loss = combined_loss(denoised_images, val_clean_images,
+                                                *Fn.loss_weights_or_default(loss_weights)).item()
         print(f"Epoch [{epoch + 1}/{num_epochs}], Validation Loss: {validation_loss:.4f}")
         if writer is not None:
             writer.add_scalar('Loss/validation', validation_loss, epoch + 1)
@@ -312,7 +320,9 @@ def train(args, train_loader=None, val_loader=None):
     start_epoch = load_checkpoint(model, optimizer, scheduler, args.checkpoint_path)
     train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, args.output_dir,
                              args.distribution_choice, num_epochs=args.num_epochs, start_epoch=start_epoch,
-                             accumulation=getattr(args, "accumulation", "reference"))
+                             accumulation=getattr(args, "accumulation", "reference"),
+                             loss_weights=(getattr(args, "mse_weight", 0.0), getattr(args, "charbonnier_weight", 1.0),
+                                           getattr(args, "ssim_weight", 0.0)))
     final_model_path = os.path.join(args.output_dir, "diffusion_RDUNet_model_checkpointed_final.pth")
     torch.save(model.state_dict(), final_model_path)
     print(f"Final model saved at {final_model_path}")
@@ -321,7 +331,8 @@ def train(args, train_loader=None, val_loader=None):
 
 
 def build_parser():
-    """diffusion_RDUnet.py:293-309, plus --dtype."""
+    """diffusion_RDUnet.py:293-309, plus --dtype, --accumulation and the three
+    weights of ``combined_loss`` (:60)."""
     parser = argparse.ArgumentParser(description="Train a diffusion model with optional optimizer and scheduler choice.")
     parser.add_argument('--dataset_choice', type=str, default='SIDD', choices=['DIV2K', 'SIDD'])
     parser.add_argument('--checkpoint_path', type=str, default=None)
@@ -343,6 +354,9 @@ def build_parser():
     parser.add_argument('--accumulation', type=str, default='reference', choices=list(ACCUMULATION_MODES),
                         help="reference: only every 4th batch's gradient is applied (the reference's rule, "
                              "without the discarded backward passes); fixed: accumulate 4 batches")
+    parser.add_argument('--mse_weight', type=float, default=0.0)
+    parser.add_argument('--charbonnier_weight', type=float, default=1.0)
+    parser.add_argument('--ssim_weight', type=float, default=0.0, help="weight of 1 - SSIM (gaussian 11x11)")
     return parser
 
 

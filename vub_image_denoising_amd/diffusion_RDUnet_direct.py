@@ -33,7 +33,9 @@ def _sample(model, x):
 
 
 def train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, num_epochs=10,
-                             start_epoch=0, accumulation_steps=4, clip_value=1.0, *, accumulation='reference'):
+                             start_epoch=0, accumulation_steps=4, clip_value=1.0, *, accumulation='reference',
+                             loss_weights=None):
     """diffusion_RDUnet_direct.py:266-327 (validation with direct_sampling)."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, CHECKPOINT_DIR, 'uniform', num_epochs,
-               start_epoch, accumulation_steps, clip_value, 1, sample=_sample, accumulation=accumulation)
+               start_epoch, accumulation_steps, clip_value, 1, sample=_sample, accumulation=accumulation,
+               loss_weights=loss_weights)

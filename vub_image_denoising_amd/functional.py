@@ -4,6 +4,8 @@
 * ``interpolate``      — ``alpha*noisy + (1-alpha)*clean`` (diffusion_RDUnet.py:99-100, :33-36)
 * ``charbonnier_loss`` / ``combined_loss`` — diffusion_RDUnet.py:57-65, fused
   forward reduction (Charbonnier and MSE in one pass) and fused backward
+* ``ssim_fused``       — the SSIM term of ``combined_loss`` (pytorch_msssim.ssim,
+  diffusion_RDUnet.py:60-65): ``rdn_ssim_fwd`` forward, ``rdn_ssim_bwd`` backward
 * ``clip_grad_norm_``  — torch.nn.utils.clip_grad_norm_ (diffusion_RDUnet.py:113)
   on the flat gradient buffer: one norm reduction + one scale, coefficient kept
   on the device
@@ -41,9 +43,31 @@ def interpolate(clean: torch.Tensor, noisy: torch.Tensor, tnorm: torch.Tensor) -
     return x
 
 
+def _ssim_launch(lib, x, y, data_range, want_coef):
+    """``rdn_ssim_fwd`` on fp32 NCHW x, y: (mean SSIM as a 1-element device tensor, the
+    three derivative maps kept for ``rdn_ssim_bwd`` or None)."""
+    if x.dim() != 4 or x.shape != y.shape:
+        raise RuntimeError("ssim: need two [N, C, H, W] tensors of one shape")
+    n, c, h, w = x.shape
+    ws = torch.empty(max(lib.rdn_ssim_workspace_size(n, c, h, w) // 4, 1), dtype=torch.float32, device=x.device)
+    coef = None
+    if want_coef and h > 10 and w > 10:
+        coef = torch.empty((3, n, c, h - 10, w - 10), dtype=torch.float32, device=x.device)
+    out = torch.empty(1, dtype=torch.float32, device=x.device)
+    H.check(lib.rdn_ssim_fwd(x.data_ptr(), y.data_ptr(), n, c, h, w, float(data_range), H.ptr(coef), ws.data_ptr(),
+                             out.data_ptr(), H.stream_ptr()), "ssim_fwd")
+    return out, coef
+
+
+def _ssim_grad(lib, x, y, coef, weight, g, dx, accumulate):
+    n, c, h, w = x.shape
+    H.check(lib.rdn_ssim_bwd(x.data_ptr(), y.data_ptr(), coef.data_ptr(), n, c, h, w, float(weight), g.data_ptr(),
+                             dx.data_ptr(), int(accumulate), H.stream_ptr()), "ssim_bwd")
+
+
 class _CombinedLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, target, wm, wc, eps):
+    def forward(ctx, pred, target, wm, wc, eps, wss=0.0):
         pred, target = _f32c(pred), _f32c(target)
         n = pred.numel()
         lib = H.lib()
@@ -51,32 +75,56 @@ class _CombinedLoss(torch.autograd.Function):
         out = torch.empty(2, dtype=torch.float32, device=pred.device)
         H.check(lib.rdn_charbonnier_fwd(pred.data_ptr(), target.data_ptr(), n, eps, ws.data_ptr(), out.data_ptr(),
                                         H.stream_ptr()), "charbonnier_fwd")
-        ctx.save_for_backward(pred, target)
-        ctx.wm, ctx.wc, ctx.eps = float(wm), float(wc), float(eps)
+        ctx.wm, ctx.wc, ctx.eps, ctx.wss = float(wm), float(wc), float(eps), float(wss)
         # mse_weight * mse + charbonnier_weight * charbonnier (diffusion_RDUnet.py:65)
-        return ctx.wm * out[1] + ctx.wc * out[0]
+        loss = ctx.wm * out[1] + ctx.wc * out[0]
+        if ctx.wss == 0.0:
+            ctx.save_for_backward(pred, target)
+            return loss
+        s, coef = _ssim_launch(lib, pred, target, 1.0, ctx.needs_input_grad[0])
+        ctx.save_for_backward(pred, target, coef)
+        return loss + ctx.wss * (1 - s[0])                     # + ssim_weight * (1 - ssim)
 
     @staticmethod
     def backward(ctx, g):
-        pred, target = ctx.saved_tensors
+        pred, target = ctx.saved_tensors[:2]
         g = _f32c(g.reshape(1))
         dp = torch.empty_like(pred)
         H.check(H.lib().rdn_charbonnier_bwd(pred.data_ptr(), target.data_ptr(), pred.numel(), ctx.eps, ctx.wc, ctx.wm,
                                             g.data_ptr(), dp.data_ptr(), H.stream_ptr()), "charbonnier_bwd")
+        if ctx.wss != 0.0:   # d(wss * (1 - ssim))/dpred, added onto the same buffer
+            _ssim_grad(H.lib(), pred, target, ctx.saved_tensors[2], -ctx.wss, g, dp, True)
         dt = -dp if ctx.needs_input_grad[1] else None
-        return dp, dt, None, None, None
+        return dp, dt, None, None, None, None
+
+
+class _SsimFused(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, data_range):
+        x, y = _f32c(x), _f32c(y)
+        s, coef = _ssim_launch(H.lib(), x, y, data_range, ctx.needs_input_grad[0])
+        ctx.save_for_backward(x, y, coef)
+        return s[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, coef = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        _ssim_grad(H.lib(), x, y, coef, 1.0, _f32c(g.reshape(1)), dx, False)
+        return dx, None, None
 
 
 def charbonnier_loss(pred, target, epsilon=1e-3):
     """mean(sqrt((pred-target)^2 + eps^2)), diffusion_RDUnet.py:57-58."""
     H.require_device(pred, target)
-    return _CombinedLoss.apply(pred, target, 0.0, 1.0, epsilon)
+    return _CombinedLoss.apply(pred, target, 0.0, 1.0, epsilon, 0.0)
 
 
 def ssim(x, y, data_range=1.0, win_size=11, win_sigma=1.5, K=(0.01, 0.03)):
     """pytorch_msssim.ssim (v1.0.0) restated with torch ops (gaussian 11x11,
-    sigma 1.5, valid padding, size_average).  Only evaluated when
-    ``ssim_weight != 0``; every reference caller uses weight 0."""
+    sigma 1.5, valid padding, size_average): the definition ``ssim_fused``
+    implements, the float64 reference of its tests, and the path of CPU tensors,
+    of a target that needs a gradient and of a non-default window or K."""
     C = x.size(1)
     coords = torch.arange(win_size, dtype=x.dtype, device=x.device) - win_size // 2
     g = torch.exp(-(coords ** 2) / (2 * win_sigma ** 2))
@@ -96,15 +144,36 @@ def ssim(x, y, data_range=1.0, win_size=11, win_sigma=1.5, K=(0.01, 0.03)):
     return torch.flatten(ssim_map, 2).mean(-1).mean()
 
 
+def ssim_fused(x, y, data_range=1.0):
+    """``ssim(x, y, data_range)`` with the default window as two launches
+    (``rdn_ssim_fwd`` / ``rdn_ssim_bwd``): the mean SSIM as a device scalar,
+    differentiable by ``x``.  CPU tensors and a ``y`` that needs a gradient take
+    the torch-op ``ssim``."""
+    if not (x.is_cuda and y.is_cuda) or (torch.is_grad_enabled() and y.requires_grad):
+        return ssim(x, y, data_range=data_range)
+    return _SsimFused.apply(x, y, float(data_range))
+
+
 def combined_loss(pred, target, mse_weight=0, charbonnier_weight=1, ssim_weight=0, epsilon=1e-3):
     """diffusion_RDUnet.py:60-65.  MSE and Charbonnier come out of one fused
     reduction; the weight-0 MSE term is still evaluated so a NaN/inf in pred
-    propagates exactly as in the reference (0*inf = NaN)."""
+    propagates exactly as in the reference (0*inf = NaN).  A non-zero
+    ``ssim_weight`` adds the fused SSIM launches to the same autograd node (the
+    torch-op ``ssim`` when the target needs a gradient)."""
     H.require_device(pred, target)
-    loss = _CombinedLoss.apply(pred, target, float(mse_weight), float(charbonnier_weight), epsilon)
-    if ssim_weight != 0:
-        loss = loss + ssim_weight * (1 - ssim(pred, target, data_range=1.0))
-    return loss
+    if ssim_weight != 0 and torch.is_grad_enabled() and target.requires_grad:
+        loss = _CombinedLoss.apply(pred, target, float(mse_weight), float(charbonnier_weight), epsilon, 0.0)
+        return loss + ssim_weight * (1 - ssim(pred, target, data_range=1.0))
+    return _CombinedLoss.apply(pred, target, float(mse_weight), float(charbonnier_weight), epsilon, float(ssim_weight))
+
+
+def loss_weights_or_default(loss_weights):
+    """``(mse, charbonnier, ssim)`` weights of ``combined_loss``; None: the
+    reference's defaults (0, 1, 0)."""
+    if loss_weights is None:
+        return (0.0, 1.0, 0.0)
+    wm, wc, wss = loss_weights
+    return (float(wm), float(wc), float(wss))
 
 
 def clip_grad_norm_flat(fp: FlatParams, max_norm: float, pre_scale: float = 1.0, want_norm: bool = True):

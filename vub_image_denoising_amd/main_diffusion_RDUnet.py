@@ -42,9 +42,11 @@ def make_training_objects(base_filters=32, lr=2e-4, dev=None, model_cls=None):
     return unet, model, optimizer, scheduler
 
 
-def train_step_checkpointed(model, clean_images, noisy_images, optimizer, accumulation_steps, clip_value=0.1):
+def train_step_checkpointed(model, clean_images, noisy_images, optimizer, accumulation_steps, clip_value=0.1, *,
+                            loss_weights=None):
     """main_diffusion_RDUnet.py:237-273 (uniform t; returns ``loss.item()``)."""
-    return train_step_device(model, clean_images, noisy_images, optimizer, 'uniform', clip_value).item()
+    return train_step_device(model, clean_images, noisy_images, optimizer, 'uniform', clip_value,
+                             loss_weights=loss_weights).item()
 
 
 def _sample(model, x):
@@ -52,10 +54,12 @@ def _sample(model, x):
 
 
 def train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, num_epochs=10,
-                             start_epoch=0, accumulation_steps=4, clip_value=1.0, *, accumulation='reference'):
+                             start_epoch=0, accumulation_steps=4, clip_value=1.0, *, accumulation='reference',
+                             loss_weights=None):
     """main_diffusion_RDUnet.py:275-336."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, CHECKPOINT_DIR, 'uniform', num_epochs,
-               start_epoch, accumulation_steps, clip_value, 1, sample=_sample, accumulation=accumulation)
+               start_epoch, accumulation_steps, clip_value, 1, sample=_sample, accumulation=accumulation,
+               loss_weights=loss_weights)
 
 
 def load_checkpoint(model, optimizer, scheduler, checkpoint_path):

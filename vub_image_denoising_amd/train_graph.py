@@ -32,6 +32,7 @@ import torch
 
 from .diffusion_RDUnet import sample_biased, train_step_device
 from .engine import find_flat
+from .functional import loss_weights_or_default
 from .optim import FusedAdam
 
 
@@ -86,11 +87,12 @@ def _node_count(g):
 
 class TrainStepGraph:
     def __init__(self, model, optimizer, shape, distribution_choice='uniform', clip_value=1.0, t_input=False,
-                 warmup=2):
+                 warmup=2, loss_weights=None):
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("TrainStepGraph needs the fused optimizer (optim.FusedAdam / FusedAdamW)")
         self.model, self.opt = model, optimizer
         self.dist, self.clip = distribution_choice, clip_value
+        self.loss_weights = loss_weights    # (mse, charbonnier, ssim) of combined_loss; None: (0, 1, 0)
         dev = next(model.parameters()).device
         self.dev = dev
         self.clean = torch.zeros(shape, dtype=torch.float32, device=dev)
@@ -102,20 +104,22 @@ class TrainStepGraph:
 
     # ------------------------------------------------------------------
     def _hyper(self):
-        """Everything baked into the captured graph: hyperparameters, the compute
-        dtype, and the addresses of the buffers the optimizer updates (a rebound
-        optimizer or a re-flattened model re-captures instead of replaying onto
-        freed memory)."""
+        """Everything baked into the captured graph: hyperparameters, the loss
+        weights, the compute dtype, and the addresses of the buffers the optimizer
+        updates (a rebound optimizer or a re-flattened model re-captures instead of
+        replaying onto freed memory)."""
         g = self.opt.param_groups[0]
         o = self.opt
         ptrs = tuple(0 if b is None else b.data_ptr()
                      for b in (getattr(o, "_m", None), getattr(o, "_v", None), o._step_dev,
                                None if o._fp is None else o._fp.flat))
         return (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), float(self.clip),
-                float(self.opt.grad_scale), self.model.unet.compute_dtype, ptrs)
+                float(self.opt.grad_scale), self.model.unet.compute_dtype, ptrs,
+                loss_weights_or_default(self.loss_weights))
 
     def _body(self):
-        loss = train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t)
+        loss = train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t,
+                                 loss_weights=self.loss_weights)
         self.opt.step()
         return loss
 
@@ -127,7 +131,8 @@ class TrainStepGraph:
         with torch.cuda.stream(side):
             if find_flat(params) is None or self.opt._fp is None:
                 # gradients as flat views, so the optimizer can bind (no update yet)
-                train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t)
+                train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t,
+                                  loss_weights=self.loss_weights)
             self.opt.use_device_step()
             fp, opt = self.opt._fp, self.opt
             snap = (fp.flat.clone(), opt._m.clone(), opt._v.clone(), opt._step)
@@ -188,10 +193,11 @@ class TrainStepGraphs:
     and the device step counter), and replays run one after another on the stream,
     so the alternation is the same sequence of steps as eager training."""
 
-    def __init__(self, model, optimizer, distribution_choice='uniform', clip_value=1.0, t_input=False, warmup=2):
+    def __init__(self, model, optimizer, distribution_choice='uniform', clip_value=1.0, t_input=False, warmup=2,
+                 loss_weights=None):
         self.model, self.opt = model, optimizer
         self.kw = dict(distribution_choice=distribution_choice, clip_value=clip_value, t_input=t_input,
-                       warmup=warmup)
+                       warmup=warmup, loss_weights=loss_weights)
         self.graphs = {}
         self.captures = 0
 

@@ -183,6 +183,8 @@ def _wgrad(dt, gather, N, h, w, hin, win, A, a_ps, a_c0, mdim, B, b_ps, b_c0, nd
     (1, 8, 8, 160, 160, 64, 64),
     (2, 16, 16, 32, 32, 3, 8),      # output conv: 3 real rows, zero-padded dY
     (1, 32, 32, 640, 640, 256, 256),
+    (1, 8, 16, 24, 24, 32, 32),     # 8-channel chunks: wgrad3_halo_kernel<f32,32,8> / wgrad3_rows_kernel<32,8>
+    (1, 13, 21, 96, 96, 32, 32),    # ragged tiles: wgrad3_glds_kernel<32,96> / wgrad3_halo_kernel<f32,32,32>
 ])
 def test_conv3x3_backward(dt, N, Hh, Ww, cin, Cs, cout, cpad):
     """dgrad (as a conv with rotated/transposed packed weights) and wgrad vs autograd."""

@@ -6,7 +6,7 @@
 // Block = 256 threads (4 waves) = a TH x TW = 8 x 16 output-pixel tile of one
 // image x BN output channels.  The input channels are walked in chunks of CK:
 // a chunk's (TH+2) x (TW+2) halo tile is loaded ONCE into LDS and feeds all 9
-// taps (the generic gather re-reads every input pixel 9x through L2).  The
+// taps (a per-tap gather would re-read every input pixel 9x through L2).  The
 // weights stream through a double-buffered LDS stage of 128 bytes per output
 // channel (one tap of 64 bf16 / 32 fp32 channels, or several taps of a smaller
 // chunk).  The next chunk's halo is prefetched into registers during the
@@ -460,11 +460,18 @@ int launch_h(const rdn_conv_desc* d, hipStream_t st, int splits = 0, float* ws =
   const int64_t blocks = (int64_t)d->n * tiles_x * tiles_y * ((d->ncols + BN - 1) / BN);
   dim3 grid((unsigned)blocks);
   if (splits > 0) {   // split-K slices (rdn_conv_fwd_splitk); no gate / gate-out here
-    const int nch = d->cin / CK, c_per = (nch + splits - 1) / splits;
-    RDN_PROBE("conv3_halo_kernel<%s,%d,%d,%d,split>", rdn_tname<T>(), BN, WMW, CK);
-    conv3_halo_kernel<T, BN, WMW, CK, false, false, true><<<dim3((unsigned)blocks, (nch + c_per - 1) / c_per), NT, 0, st>>>(
-        *d, tiles_x, tiles_y, c_per, ws);
-    return rdn_check_launch("rdn_conv_fwd_splitk(conv3)");
+    // a split needs >= 2 channel chunks (rdn_conv3_splitk_slices) and the whole-row chunks
+    // (48 / 80 / 96) are always the only one: built for the power-of-two chunks only
+    if constexpr ((CK & (CK - 1)) == 0) {
+      const int nch = d->cin / CK, c_per = (nch + splits - 1) / splits;
+      RDN_PROBE("conv3_halo_kernel<%s,%d,%d,%d,split>", rdn_tname<T>(), BN, WMW, CK);
+      conv3_halo_kernel<T, BN, WMW, CK, false, false, true><<<dim3((unsigned)blocks, (nch + c_per - 1) / c_per), NT, 0, st>>>(
+          *d, tiles_x, tiles_y, c_per, ws);
+      return rdn_check_launch("rdn_conv_fwd_splitk(conv3)");
+    } else {
+      rdn_set_error("rdn_conv_fwd_splitk(conv3): no split with one %d-channel chunk", CK);
+      return RDN_E_SHAPE;
+    }
   }
   constexpr bool CP = can_pair<T, BN, CK>;
   const bool pair = CP && blocks <= 2 * (int64_t)rdn_cu_count();
@@ -544,6 +551,26 @@ int launch_bn(const rdn_conv_desc* d, hipStream_t st, int splits = 0, float* ws 
   return RDN_E_ARG;
 }
 
+// (dtype, channel chunk) -> launch_bn<T, CK>, for the plain launch and the split-K slices
+int launch_ck(const rdn_conv_desc* d, int ck, hipStream_t st, int splits = 0, float* ws = nullptr) {
+  if (d->dtype == RDN_BF16) {
+    switch (ck) {
+      case 96: return launch_bn<bf16, 96>(d, st, splits, ws);
+      case 80: return launch_bn<bf16, 80>(d, st, splits, ws);
+      case 48: return launch_bn<bf16, 48>(d, st, splits, ws);
+      case 64: return launch_bn<bf16, 64>(d, st, splits, ws);
+      case 32: return launch_bn<bf16, 32>(d, st, splits, ws);
+      case 16: return launch_bn<bf16, 16>(d, st, splits, ws);
+      default: return launch_bn<bf16, 8>(d, st, splits, ws);
+    }
+  }
+  switch (ck) {
+    case 32: return launch_bn<float, 32>(d, st, splits, ws);
+    case 16: return launch_bn<float, 16>(d, st, splits, ws);
+    default: return launch_bn<float, 8>(d, st, splits, ws);
+  }
+}
+
 }  // namespace
 
 int rdn_conv3_chunk_pow2(int cin, int cap) {
@@ -592,21 +619,8 @@ int rdn_conv3_launch(const rdn_conv_desc* d, hipStream_t st) {
     if (wsd <= 0) return wsd;
     const int ws = rdn_conv3_ws_launch(d, ck, st);
     if (ws <= 0) return ws;
-    switch (ck) {
-      case 96: return launch_bn<bf16, 96>(d, st);
-      case 80: return launch_bn<bf16, 80>(d, st);
-      case 48: return launch_bn<bf16, 48>(d, st);
-      case 64: return launch_bn<bf16, 64>(d, st);
-      case 32: return launch_bn<bf16, 32>(d, st);
-      case 16: return launch_bn<bf16, 16>(d, st);
-      default: return launch_bn<bf16, 8>(d, st);
-    }
   }
-  switch (ck) {
-    case 32: return launch_bn<float, 32>(d, st);
-    case 16: return launch_bn<float, 16>(d, st);
-    default: return launch_bn<float, 8>(d, st);
-  }
+  return launch_ck(d, ck, st);
 }
 
 // ---- split-K slices of the 3x3 forward (round 6; rdn_conv_fwd_splitk, conv_gemm.hip,
@@ -631,21 +645,5 @@ int rdn_conv3_splitk_slices(const rdn_conv_desc* d, int cus) {
 
 // the slice launch: raw fp32 sums of slice y to ws[y][pixel][ncols]
 int rdn_conv3_splitk_launch(const rdn_conv_desc* d, int splits, float* ws, hipStream_t st) {
-  const int ck = rdn_conv3_chunk_impl(d->cin, d->dtype);
-  if (d->dtype == RDN_BF16) {
-    switch (ck) {
-      case 96: return launch_bn<bf16, 96>(d, st, splits, ws);
-      case 80: return launch_bn<bf16, 80>(d, st, splits, ws);
-      case 48: return launch_bn<bf16, 48>(d, st, splits, ws);
-      case 64: return launch_bn<bf16, 64>(d, st, splits, ws);
-      case 32: return launch_bn<bf16, 32>(d, st, splits, ws);
-      case 16: return launch_bn<bf16, 16>(d, st, splits, ws);
-      default: return launch_bn<bf16, 8>(d, st, splits, ws);
-    }
-  }
-  switch (ck) {
-    case 32: return launch_bn<float, 32>(d, st, splits, ws);
-    case 16: return launch_bn<float, 16>(d, st, splits, ws);
-    default: return launch_bn<float, 8>(d, st, splits, ws);
-  }
+  return launch_ck(d, rdn_conv3_chunk_impl(d->cin, d->dtype), st, splits, ws);
 }

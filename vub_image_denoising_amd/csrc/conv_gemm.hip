@@ -5,13 +5,16 @@
 // GEMM row m is a pixel of the row grid (n, h, w); K = taps * cin with
 // k = tap * cin + ci, so every 16-byte unit a lane gathers (8 bf16 / 4 fp32
 // channels of one source pixel) is contiguous in NHWC memory.  The tap decides
-// the source pixel (RDN_G_CONV3: 3x3 pad 1; RDN_G_S2: 2x2 stride 2; RDN_G_PIX:
-// same pixel).  P is the packed weight operand [rows][kp] (k contiguous).
+// the source pixel (RDN_G_S2: 2x2 stride 2; RDN_G_PIX: same pixel).  P is the
+// packed weight operand [rows][kp] (k contiguous).
 //
-// One kernel serves the 3x3 convs of every block (Unet_model.py:48-49,60-61,
-// 72-75,35), the 2x2/s2 down-sampling conv (:26), the 2x2/s2 transposed conv
-// (:36, as a per-pixel GEMM with a depth-to-space scatter epilogue) and the
-// input gradients of all three (the same three shapes with repacked weights).
+// The kernel serves the 2x2/s2 down-sampling conv (Unet_model.py:26), the 2x2/s2
+// transposed conv (:36, as a per-pixel GEMM with a depth-to-space scatter
+// epilogue), the input gradients of both (the same two shapes with repacked
+// weights) and the split-K forms of all of these (rdn_conv_fwd_splitk), where
+// conv_pix.hip does not take the shape.  The 3x3 convs have kernels of their own:
+// rdn_conv_fwd, the entry point of every conv below, checks a RDN_G_CONV3
+// descriptor and hands it to rdn_conv3_launch (conv3_halo.hip).
 //
 // Tiling: 256 threads = 4 waves; block tile BM x BN; K staged through LDS in
 // steps of 8 units (128 B per row), double buffered with a register prefetch
@@ -27,7 +30,6 @@ constexpr int U = 8;                 // 16-byte units per LDS row per stage
 constexpr int ROWB = U * 16 + 32;    // padded LDS row: 160 B = 10 slots, conflict-free ds_read_b128
 
 template <int GATHER> struct Taps;
-template <> struct Taps<RDN_G_CONV3> { static constexpr int N = 9; };
 template <> struct Taps<RDN_G_S2> { static constexpr int N = 4; };
 template <> struct Taps<RDN_G_PIX> { static constexpr int N = 1; };
 
@@ -97,13 +99,8 @@ __global__ __launch_bounds__(NT) void conv_gemm_kernel(rdn_conv_desc d, FastDiv 
       u32x4 v = {0u, 0u, 0u, 0u};
       if (a_ok[r] && tap < TAPS) {
         int64_t off;
-        bool ok = true;
-        if (GATHER == RDN_G_CONV3) {
-          const int dy = tap / 3 - 1, dx = tap % 3 - 1;
-          const int ys = a_y[r] + dy, xs = a_x[r] + dx;
-          ok = (ys >= 0) && (ys < d.hin) && (xs >= 0) && (xs < d.win);
-          off = a_base[r] + ((int64_t)dy * d.win + dx) * d.x_ps + cf;
-        } else if (GATHER == RDN_G_S2) {
+        bool ok = true;   // (kept from the 3x3 gather's bounds test: without it the S2 kernels schedule differently)
+        if (GATHER == RDN_G_S2) {
           off = a_base[r] + ((int64_t)(tap >> 1) * d.win + (tap & 1)) * d.x_ps + cf;
         } else {
           off = a_base[r] + cf;
@@ -327,11 +324,8 @@ int launch_gather(const rdn_conv_desc* d, hipStream_t st, int splits = 0, float*
     return rdn_check_launch("rdn_conv_fwd_splitk(gemm)");
   }
   RDN_PROBE("conv_gemm_kernel<%s,%d,%d,%d,%d>", rdn_tname<T>(), BM, BN, WMW, d->gather);
-  switch (d->gather) {
-    case RDN_G_CONV3: conv_gemm_kernel<T, BM, BN, WMW, RDN_G_CONV3><<<grid, NT, 0, st>>>(*d, fw, fhw); break;
-    case RDN_G_S2: conv_gemm_kernel<T, BM, BN, WMW, RDN_G_S2><<<grid, NT, 0, st>>>(*d, fw, fhw); break;
-    default: conv_gemm_kernel<T, BM, BN, WMW, RDN_G_PIX><<<grid, NT, 0, st>>>(*d, fw, fhw); break;
-  }
+  if (d->gather == RDN_G_S2) conv_gemm_kernel<T, BM, BN, WMW, RDN_G_S2><<<grid, NT, 0, st>>>(*d, fw, fhw);
+  else conv_gemm_kernel<T, BM, BN, WMW, RDN_G_PIX><<<grid, NT, 0, st>>>(*d, fw, fhw);
   return rdn_check_launch("rdn_conv_fwd");
 }
 

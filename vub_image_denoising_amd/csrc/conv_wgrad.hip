@@ -1,16 +1,18 @@
-// Weight gradient of the implicit-GEMM convolutions (gfx950, MFMA).
+// Weight gradient of the 2x2 / stride 2 convolutions (gfx950, MFMA), the entry
+// point of every weight gradient (rdn_conv_wgrad: the 3x3 ones go on to
+// wgrad3_halo.hip) and the split reduction all of them share.
 //
 //   ws[s][m][tap*ndim + nd] = sum_{p in split s} A[p][m] * B[gather(p, tap)][nd]
 //
 // A = the per-pixel operand on the reduction grid (n, h, w): dYpre for Conv2d
 // (rows = output channels), the input X for ConvTranspose2d (rows = input
-// channels).  B = the gathered operand: X under the conv's taps (RDN_G_CONV3:
-// 3x3 pad 1 at the same resolution; RDN_G_S2: (2y+dy, 2x+dx) on the 2h x 2w
-// grid, which is both Conv2d k2 s2's input and ConvTranspose2d k2 s2's output
-// gradient).  The K dimension (pixels) is split over blockIdx.z; a second
-// kernel sums the splits in a fixed order (deterministic) and writes the
-// reference's OIHW / IOHW layout (aten convolution_backward grad_weight of
-// Unet_model.py:26,35-36,48-49,60-61,72-75).
+// channels).  B = the gathered operand (RDN_G_S2): pixel (2y+dy, 2x+dx) of the
+// 2h x 2w grid for tap (dy, dx), which is both Conv2d k2 s2's input and
+// ConvTranspose2d k2 s2's output gradient.  The K dimension (pixels) is split
+// over blockIdx.z; a second kernel sums the splits in a fixed order
+// (deterministic) and writes the reference's OIHW / IOHW layout (aten
+// convolution_backward grad_weight of Unet_model.py:26,35-36,48-49,60-61,72-75;
+// the 3x3 kernels write the same workspace layout with 9 taps).
 //
 // Pixels are staged into LDS as [pixel][channel] rows; MFMA operands need the
 // pixel (k) index contiguous per lane, so bf16 fragments come out of LDS with
@@ -22,8 +24,9 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int KP = 32;  // pixels per stage
+constexpr int TAPS = 4;  // (dy, dx) of the 2x2 window: 3x3 descriptors never reach this kernel or its launchers
 
-template <typename T, int BM, int BN, int WMW, int GATHER>
+template <typename T, int BM, int BN, int WMW>
 __global__ __launch_bounds__(NT) void wgrad_kernel(rdn_wgrad_desc d, FastDiv fd_w, FastDiv fd_hw, int pchunk) {
   constexpr int VEC = TypeInfo<T>::VEC;
   constexpr int ES = sizeof(T);
@@ -34,7 +37,6 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(rdn_wgrad_desc d, FastDiv fd_
   constexpr int A_UNITS = KP * AG, B_UNITS = KP * BG;
   constexpr int A_IT = (A_UNITS + NT - 1) / NT, B_IT = (B_UNITS + NT - 1) / NT;
   constexpr int ROWA = BM * ES + 16, ROWB = BN * ES + 16;
-  constexpr int TAPS = GATHER == RDN_G_CONV3 ? 9 : 4;
   static_assert(NT % AG == 0 && NT % BG == 0, "group");
 
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * KP * (ROWA + ROWB)];
@@ -62,9 +64,7 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(rdn_wgrad_desc d, FastDiv fd_
   // channel offsets (channel-blocked operands: rdn_coff), fixed per thread
   const int64_t a_cf = rdn_coff(d.a_c0 + am, d.a_ps, d.a_pl);
   const int64_t b_cf = rdn_coff(d.b_c0 + bnd, d.b_ps, d.b_pl);
-  int bdy, bdx;
-  if (GATHER == RDN_G_CONV3) { bdy = btap / 3 - 1; bdx = btap % 3 - 1; }
-  else { bdy = btap >> 1; bdx = btap & 1; }
+  const int bdy = btap >> 1, bdx = btap & 1;
 
   u32x4 ra[A_IT], rb[B_IT];
   auto load_stage = [&](int64_t pb) {
@@ -86,9 +86,7 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(rdn_wgrad_desc d, FastDiv fd_
         const uint32_t rem = (uint32_t)p - nimg * (uint32_t)(d.h * d.w);
         const int y = (int)fdiv(rem, fd_w);
         const int x = (int)rem - y * d.w;
-        int ys, xs;
-        if (GATHER == RDN_G_CONV3) { ys = y + bdy; xs = x + bdx; }
-        else { ys = 2 * y + bdy; xs = 2 * x + bdx; }
+        const int ys = 2 * y + bdy, xs = 2 * x + bdx;
         if (ys >= 0 && ys < d.hin && xs >= 0 && xs < d.win)
           v = *(const u32x4*)(B + (((int64_t)nimg * d.hin + ys) * d.win + xs) * d.b_ps + b_cf);
       }
@@ -277,18 +275,16 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(ReduceBatch b) 
 
 struct Cfg { int bm, bn; };
 static Cfg pick(const rdn_wgrad_desc* d) {
-  const int taps = d->gather == RDN_G_CONV3 ? 9 : 4;
   Cfg c;
   c.bm = d->mdim <= 16 ? 16 : d->mdim <= 32 ? 32 : 64;
-  c.bn = taps * d->ndim <= 64 ? 64 : 128;
+  c.bn = TAPS * d->ndim <= 64 ? 64 : 128;
   return c;
 }
 
 static int auto_splits(const rdn_wgrad_desc* d) {
   if (d->splits > 0) return d->splits;
   const Cfg c = pick(d);
-  const int taps = d->gather == RDN_G_CONV3 ? 9 : 4;
-  const int64_t tiles = (int64_t)((d->mdim + c.bm - 1) / c.bm) * ((taps * d->ndim + c.bn - 1) / c.bn);
+  const int64_t tiles = (int64_t)((d->mdim + c.bm - 1) / c.bm) * ((TAPS * d->ndim + c.bn - 1) / c.bn);
   const int64_t P = (int64_t)d->n * d->h * d->w;
   // ~2 blocks per CU (round 4, interleaved: 512 1771 / 1957, 256 1765 / 1939, 128 1767 /
   // 1941 img/s B16 / B32, profiles/r04_v31_wg2_blocks_ab.txt; RDN_WG2_BLOCKS for A/B)
@@ -302,18 +298,14 @@ static int auto_splits(const rdn_wgrad_desc* d) {
 
 template <typename T, int BM, int BN, int WMW>
 static int launch_g(const rdn_wgrad_desc* d, hipStream_t st) {
-  const int taps = d->gather == RDN_G_CONV3 ? 9 : 4;
   const int splits = auto_splits(d);
   const int64_t P = (int64_t)d->n * d->h * d->w;
   int64_t pchunk = (P + splits - 1) / splits;
   pchunk = (pchunk + KP - 1) / KP * KP;
-  dim3 grid((d->mdim + BM - 1) / BM, (taps * d->ndim + BN - 1) / BN, splits);
+  dim3 grid((d->mdim + BM - 1) / BM, (TAPS * d->ndim + BN - 1) / BN, splits);
   FastDiv fw = make_fastdiv((uint32_t)d->w), fhw = make_fastdiv((uint32_t)(d->h * d->w));
-  RDN_PROBE("wgrad_kernel<%s,%d,%d,%d,%d>", rdn_tname<T>(), BM, BN, WMW, d->gather);
-  if (d->gather == RDN_G_CONV3)
-    wgrad_kernel<T, BM, BN, WMW, RDN_G_CONV3><<<grid, NT, 0, st>>>(*d, fw, fhw, (int)pchunk);
-  else
-    wgrad_kernel<T, BM, BN, WMW, RDN_G_S2><<<grid, NT, 0, st>>>(*d, fw, fhw, (int)pchunk);
+  RDN_PROBE("wgrad_kernel<%s,%d,%d,%d>", rdn_tname<T>(), BM, BN, WMW);
+  wgrad_kernel<T, BM, BN, WMW><<<grid, NT, 0, st>>>(*d, fw, fhw, (int)pchunk);
   return rdn_check_launch("rdn_conv_wgrad");
 }
 

@@ -198,7 +198,6 @@ int rdn_conv3_big_launch(const rdn_conv_desc* d, int ck, hipStream_t st);
 int rdn_wgrad3_launch(const rdn_wgrad_desc* d, hipStream_t st);
 int rdn_wgrad3_splits(const rdn_wgrad_desc* d);
 int rdn_wgrad3_chunks(const rdn_wgrad_desc* d);
-int rdn_wgrad3_glds_pick(const rdn_wgrad_desc* d, int single_chunk, int* bm, int* ck);
 int rdn_wgrad3_glds_launch(const rdn_wgrad_desc* d, int bm, int ck, int blocks, int tiles_x, int tiles_y, int ntiles,
                            int tpb, hipStream_t st);
 

@@ -18,10 +18,11 @@
 // retires the reads of the stage the next DMA overwrites (it was read one tile
 // earlier).
 //
-// Multi-chunk (level-1..3) launches only: the single-chunk level-0/1 weight
-// gradients, where the PReLU backward is fused into the loader, stay on the rows
-// kernel (a gated variant of this one was faster alone but its one 135-KB block per
-// CU on the weight-gradient stream cost the dgrad chain more: 1490 vs 1497 img/s, r02).
+// Multi-chunk (level-1..3) launches only (plan(), wgrad3_halo.hip, decides): the
+// single-chunk level-0/1 weight gradients, where the PReLU backward is fused into the
+// loader, stay on the rows kernel (a gated variant of this one was faster alone but
+// its one 135-KB block per CU on the weight-gradient stream cost the dgrad chain
+// more: 1490 vs 1497 img/s, r02).
 //
 // LDS images.  One DMA wave-instruction writes 1 KiB contiguously (lane l ->
 // bytes l*16..l*16+15), so the images are dense rows (dY: BM*2 bytes per pixel;
@@ -37,7 +38,6 @@
 // load 16 zero bytes from a device-side zero block, so stale stage bytes never
 // reach the MFMAs.
 #include "rdn_device.h"
-
 
 #include <type_traits>
 
@@ -92,8 +92,7 @@ __device__ __forceinline__ int rot(int x) {
   if constexpr (RBYTES == 64) return (x >> 1) % U;
   else if constexpr (RBYTES == 128) return x % U;
   else if constexpr (RBYTES == 192) return ((x >> 2) * 6) % U;
-  else if constexpr (RBYTES == 256) return x % U;
-  else return 0;                                          // 32, 96, 160: conflict-free as is
+  else { static_assert(RBYTES == 160, "row size without a checked rotation"); return 0; }   // conflict-free as is
 }
 
 // DMAs wave w issues per tile: PA_ dY pieces + halo pieces w, w+4, ... < HPC;
@@ -339,9 +338,7 @@ template <int BM>
 int launch_ck(const rdn_wgrad_desc* d, int ck, int blocks, int tiles_x, int tiles_y, int ntiles, int tpb,
               hipStream_t st) {
   switch (ck) {
-    case 16: return launch<BM, 16>(d, blocks, tiles_x, tiles_y, ntiles, tpb, st);
     case 32: return launch<BM, 32>(d, blocks, tiles_x, tiles_y, ntiles, tpb, st);
-    case 48: return launch<BM, 48>(d, blocks, tiles_x, tiles_y, ntiles, tpb, st);
     case 64: return launch<BM, 64>(d, blocks, tiles_x, tiles_y, ntiles, tpb, st);
     case 80: return launch<BM, 80>(d, blocks, tiles_x, tiles_y, ntiles, tpb, st);
     case 96: return launch<BM, 96>(d, blocks, tiles_x, tiles_y, ntiles, tpb, st);
@@ -352,28 +349,9 @@ int launch_ck(const rdn_wgrad_desc* d, int ck, int blocks, int tiles_x, int tile
 
 }  // namespace
 
-// Tile shape of the LDS-DMA weight-gradient kernel for d, or 0 when it does not
-// apply.  single_chunk: the rows plan reads the whole input pixel row in one
-// channel group (the level-0/1 layers, where the PReLU gate is fused); else the
-// multi-chunk (level-1..3) launches.
-int rdn_wgrad3_glds_pick(const rdn_wgrad_desc* d, int single_chunk, int* bm, int* ck) {
-  if (single_chunk || d->dtype != RDN_BF16 || d->a_gate) return 0;
-  if (d->mdim < 32 || d->ndim % 32) return 0;
-  *bm = d->mdim <= 32 ? 32 : 64;
-  *ck = d->ndim % 64 == 0 ? 64 : 32;
-  // the narrow level-1 layers (96 / 128 / 160 input channels): whole-row or half-row
-  // channel groups, so operand A (dYpre) is read 1-2 times instead of 2-5 (per-layer
-  // A/B, r03_v6: level-1 conv_1 / conv_3 weight gradients -10..-20 %, up_0 -28 %)
-  if (d->ndim <= 160) {
-    if (d->ndim % 96 == 0) *ck = 96;
-    else if (d->ndim % 80 == 0) *ck = 80;   // (128 as one group: 43 -> 45 us, kept at 2 x 64)
-  }
-  return 1;
-}
-
+// the tile shapes plan() (wgrad3_halo.hip) picks: bm in {32, 64} x ck in {32, 64, 80, 96}
 int rdn_wgrad3_glds_launch(const rdn_wgrad_desc* d, int bm, int ck, int blocks, int tiles_x, int tiles_y, int ntiles,
                            int tpb, hipStream_t st) {
-  if (bm == 16) return launch_ck<16>(d, ck, blocks, tiles_x, tiles_y, ntiles, tpb, st);
   if (bm == 32) return launch_ck<32>(d, ck, blocks, tiles_x, tiles_y, ntiles, tpb, st);
   if (bm == 64) return launch_ck<64>(d, ck, blocks, tiles_x, tiles_y, ntiles, tpb, st);
   rdn_set_error("rdn_conv_wgrad(conv3 glds): BM=%d", bm);

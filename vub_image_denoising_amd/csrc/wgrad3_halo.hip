@@ -3,19 +3,24 @@
 //
 //   ws[split][co][tap*ndim + ci] = sum_p dYpre[p][co] * X[p + tap][ci]
 //
-// Block = (BM output channels) x (one CK-channel chunk of the input) x a range
-// of 8 x 16 pixel tiles.  Per tile the dYpre tile [128 px][BM] and the input
-// halo [(8+2) x (16+2) px][CK] are staged into LDS ONCE and feed all 9 taps
-// (the generic path re-gathers the input once per tap), giving BM x 9*CK
-// accumulators per block with K = 128 pixels per tile.
+// Every 3x3 weight gradient comes here (rdn_conv_wgrad; the 2x2 ones are
+// conv_wgrad.hip's).  Block = (BM output channels) x (one CK-channel chunk of the
+// input) x a range of 8 x 16 pixel tiles.  Per tile the dYpre tile [128 px][BM]
+// and the input halo [(8+2) x (16+2) px][CK] are staged into LDS ONCE and feed
+// all 9 taps, giving BM x 9*CK accumulators per block with K = 128 pixels per tile.
 //
-// MFMA operands need the pixel (k) index along each lane's 8 elements, so
-// bf16 fragments come out of LDS with ds_read_b64_tr_b16 (each 16-lane group
-// reads 4 pixel rows x 16 channels and gets it transposed).  Lane group g
-// takes pixels {4g..4g+3} then {16+4g..16+4g+3} of a 32-pixel k-step, so the
-// 8 rows a half-wave touches are consecutive: with the padded row strides
-// below every transpose read is bank-conflict free.  fp32 takes one pixel per
-// lane group (v_mfma_f32_16x16x4_f32) with plain ds_read_b32.
+// Two kernels, one per storage type, and plan() below, which also routes the
+// multi-chunk bf16 shapes to the LDS-DMA kernel of wgrad3_glds.hip:
+//   wgrad3_halo_kernel   fp32: one pixel per lane group (v_mfma_f32_16x16x4_f32)
+//                        with plain ds_read_b32, power-of-two chunks of <= 32 channels
+//   wgrad3_rows_kernel   bf16: MFMA operands need the pixel (k) index along each
+//                        lane's 8 elements, so fragments come out of LDS with
+//                        ds_read_b64_tr_b16 (each 16-lane group reads 4 pixel rows x
+//                        16 channels and gets it transposed).  Lane group g takes
+//                        pixels {4g..4g+3} then {16+4g..16+4g+3} of a 32-pixel k-step,
+//                        so the 8 rows a half-wave touches are consecutive: with the
+//                        padded row strides below every transpose read is
+//                        bank-conflict free.  Channel groups of up to 96 (whole rows)
 //
 // The dYpre tile of image pixels outside the image is zero, so partial tiles
 // contribute nothing.  Splits are summed by rdn_wgrad_reduce (fixed order).
@@ -36,17 +41,16 @@ constexpr int tr_stride(int bytes) {
 // fp32 (ds_read_b32, rows g and g+1 in one half-wave): stride = 64 (mod 128) bytes
 constexpr int f32_stride(int bytes) { return bytes % 128 <= 64 ? bytes - bytes % 128 + 64 : bytes - bytes % 128 + 192; }
 
-template <typename T, int BM, int CK, bool GATE>
+template <int BM, int CK, bool GATE>
 __global__ __launch_bounds__(NT, 2) void wgrad3_halo_kernel(rdn_wgrad_desc d, int tiles_x, int tiles_y, int ntiles,
                                                             int tiles_per_block) {
-  constexpr int ES = sizeof(T);
-  constexpr int VEC = TypeInfo<T>::VEC;
+  constexpr int VEC = 4;                    // floats per 16-byte unit
   constexpr int NCOL = 9 * CK;
   constexpr int NT_ALL = (NCOL + 15) / 16;
   constexpr int NTW = (NT_ALL + 3) / 4;     // n-tiles per wave
   constexpr int MT = BM / 16;
-  constexpr int DROW = ES == 2 ? tr_stride(BM * ES) : f32_stride(BM * ES);
-  constexpr int HROW = ES == 2 ? tr_stride(CK * ES) : f32_stride(CK * ES);
+  constexpr int DROW = f32_stride(BM * 4);
+  constexpr int HROW = f32_stride(CK * 4);
   constexpr int D_UNITS = TP * (BM / VEC), H_UNITS = HP * (CK / VEC);
   constexpr int D_IT = (D_UNITS + NT - 1) / NT, H_IT = (H_UNITS + NT - 1) / NT;
   constexpr int D_BYTES = TP * DROW;
@@ -62,15 +66,15 @@ __global__ __launch_bounds__(NT, 2) void wgrad3_halo_kernel(rdn_wgrad_desc d, in
   const int c0 = blockIdx.y * CK;
   const int t_beg = blockIdx.z * tiles_per_block;
   const int t_end = min(t_beg + tiles_per_block, ntiles);
-  const T* __restrict__ A = (const T*)d.a;
-  const T* __restrict__ Bx = (const T*)d.b;
+  const float* __restrict__ A = (const float*)d.a;
+  const float* __restrict__ Bx = (const float*)d.b;
   const int H = d.h, W = d.w;
 
   u32x4 dreg[D_IT], hreg[H_IT];
   // PReLU-backward gate on A (dY -> dYpre) + dalpha / dbias partials
   static_assert(NT % (BM / VEC) == 0, "fixed channel group per thread");
   u32x4 greg[GATE ? D_IT : 1];
-  const T* __restrict__ G = (const T*)d.a_gate;
+  const float* __restrict__ G = (const float*)d.a_gate;
   const int acg = tid % (BM / VEC);           // this thread's A channel group
   float galpha[GATE ? VEC : 1], sa[GATE ? VEC : 1], sb[GATE ? VEC : 1];
   const bool do_part = GATE && d.part != nullptr && blockIdx.y == 0;
@@ -134,12 +138,12 @@ __global__ __launch_bounds__(NT, 2) void wgrad3_halo_kernel(rdn_wgrad_desc d, in
         u32x4 v = dreg[it];
         if constexpr (GATE) {
           float dy[VEC], pr[VEC];
-          Unit16<T>::unpack(v, dy);
-          Unit16<T>::unpack(greg[it], pr);
+          Unit16<float>::unpack(v, dy);
+          Unit16<float>::unpack(greg[it], pr);
 #pragma unroll
           for (int q = 0; q < VEC; ++q) rdn_prelu_bwd1(dy[q], pr[q], galpha[q], true, sa[q]);
-          v = Unit16<T>::pack(dy);
-          if (do_part) {  // dbias sums dYpre before its rounding to T, as rdn_prelu_bwd does
+          v = Unit16<float>::pack(dy);
+          if (do_part) {  // dbias sums dYpre, as rdn_prelu_bwd does
 #pragma unroll
             for (int q = 0; q < VEC; ++q) sb[q] += dy[q];
           }
@@ -168,8 +172,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad3_halo_kernel(rdn_wgrad_desc d, in
 #pragma unroll
   for (int j = 0; j < NTW; ++j) {
     const int nt = wave + 4 * j;
-    // bf16: lane supplies columns (4p .. 4p+3) of the tile; fp32: column li
-    const int c = nt * 16 + (ES == 2 ? 4 * (li & 3) : li);
+    const int c = nt * 16 + li;               // the lane supplies column li of the tile
     const int cc = (nt < NT_ALL && c < NCOL) ? c : 0;
     col_tap[j] = cc / CK;
     col_ci[j] = cc - (cc / CK) * CK;
@@ -182,49 +185,20 @@ __global__ __launch_bounds__(NT, 2) void wgrad3_halo_kernel(rdn_wgrad_desc d, in
   __syncthreads();
   for (int t = t_beg; t < t_end; ++t) {
     if (t + 1 < t_end) load_tile(t + 1);
-    if constexpr (ES == 2) {
-      const int q = li >> 2, pp = li & 3;
-#pragma unroll
-      for (int ks = 0; ks < TP / 32; ++ks) {
-        // k slots of group g: pixels ks*32 + {4g+q} and ks*32 + 16 + {4g+q}
-        const int pa = ks * 32 + 4 * g + q, pb = pa + 16;
-        bf16x8 af[MT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(RDN_LDS_PTR(i16x4, dyl + pa * DROW + (i * 16 + 4 * pp) * 2));
-          const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(RDN_LDS_PTR(i16x4, dyl + pb * DROW + (i * 16 + 4 * pp) * 2));
-          af[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
-        const int pya = pa >> 4, pxa = pa & 15, pyb = pb >> 4, pxb = pb & 15;
-#pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-          if (wave + 4 * j >= NT_ALL) continue;
-          const int tp = col_tap[j], ky = tp / 3, kx = tp - 3 * ky;
-          const unsigned char* ba = hal + ((pya + ky) * (TW + 2) + pxa + kx) * HROW + col_ci[j] * 2;
-          const unsigned char* bb = hal + ((pyb + ky) * (TW + 2) + pxb + kx) * HROW + col_ci[j] * 2;
-          const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(RDN_LDS_PTR(i16x4, ba));
-          const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(RDN_LDS_PTR(i16x4, bb));
-          const bf16x8 bfr = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-#pragma unroll
-          for (int i = 0; i < MT; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr, acc[i][j], 0, 0, 0);
-        }
-      }
-    } else {
 #pragma unroll 4
-      for (int e = 0; e < TP / 4; ++e) {
-        const int p = 4 * e + g;
-        const int py = p >> 4, px = p & 15;
-        float af[MT];
+    for (int e = 0; e < TP / 4; ++e) {
+      const int p = 4 * e + g;
+      const int py = p >> 4, px = p & 15;
+      float af[MT];
 #pragma unroll
-        for (int i = 0; i < MT; ++i) af[i] = *(const float*)(dyl + p * DROW + (i * 16 + li) * 4);
+      for (int i = 0; i < MT; ++i) af[i] = *(const float*)(dyl + p * DROW + (i * 16 + li) * 4);
 #pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-          if (wave + 4 * j >= NT_ALL) continue;
-          const int tp = col_tap[j], ky = tp / 3, kx = tp - 3 * ky;
-          const float b = *(const float*)(hal + ((py + ky) * (TW + 2) + px + kx) * HROW + col_ci[j] * 4);
+      for (int j = 0; j < NTW; ++j) {
+        if (wave + 4 * j >= NT_ALL) continue;
+        const int tp = col_tap[j], ky = tp / 3, kx = tp - 3 * ky;
+        const float b = *(const float*)(hal + ((py + ky) * (TW + 2) + px + kx) * HROW + col_ci[j] * 4);
 #pragma unroll
-          for (int i = 0; i < MT; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], b, acc[i][j], 0, 0, 0);
-        }
+        for (int i = 0; i < MT; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], b, acc[i][j], 0, 0, 0);
       }
     }
     __syncthreads();
@@ -280,14 +254,21 @@ __global__ __launch_bounds__(NT, 2) void wgrad3_halo_kernel(rdn_wgrad_desc d, in
   }
 }
 
-// bf16 variant with wide channel groups (CK up to 96: whole level-0 pixel rows,
+// The bf16 kernel: wide channel groups (CK up to 96: whole level-0 pixel rows,
 // so dY and X are each read once per launch in full rows) and no per-tile
 // index math in the k loop: every LDS operand address is a per-thread base
 // fixed for the launch plus an immediate, and the tile loaders add one
 // precomputed per-unit offset to a per-tile base.
+//
+// Accumulator budget BM x CK <= ROWS_ACC (BM x 9 CK accumulators per block): two
+// blocks per CU (measured r01: a 4096 budget at one block per CU, and 128-channel
+// blocks, were slower).  plan() picks within it and nothing larger is built.
+constexpr int ROWS_ACC = 2560;
+
 template <int BM, int CK, bool GATE>
-__global__ __launch_bounds__(NT, (BM * CK > 2560 ? 1 : 2)) void wgrad3_rows_kernel(rdn_wgrad_desc d, int tiles_x, int tiles_y, int ntiles,
+__global__ __launch_bounds__(NT, 2) void wgrad3_rows_kernel(rdn_wgrad_desc d, int tiles_x, int tiles_y, int ntiles,
                                                             int tiles_per_block) {
+  static_assert(BM * CK <= ROWS_ACC, "two blocks per CU");
   constexpr int VEC = 8;
   constexpr int NCOL = 9 * CK;
   constexpr int NT_ALL = (NCOL + 15) / 16;
@@ -534,85 +515,90 @@ __global__ __launch_bounds__(NT, (BM * CK > 2560 ? 1 : 2)) void wgrad3_rows_kern
   }
 }
 
-struct Plan { int bm, ck, rows, glds, mtiles, chunks, tiles_x, tiles_y, ntiles, tpb, splits, chunks_rows; };
+// ---- the one plan of a 3x3 weight gradient: kernel, tile shape, grid and splits
+enum Kind { GLDS, ROWS, F32 };   // wgrad3_glds_kernel (wgrad3_glds.hip) / wgrad3_rows_kernel / wgrad3_halo_kernel
+struct Plan { Kind kind; int bm, ck, mtiles, chunks, tiles_x, tiles_y, ntiles, tpb, splits, chunks_rows; };
+
+// Split-K slices over the pixel tiles: `target` blocks per launch over `base` (m-tile,
+// chunk) pairs, at least `min_tiles` tiles per block; d->splits > 0 overrides the target.
+// Blocks past the last tile write zero slabs, so any count is exact.
+struct SplitRule { int target; bool ceil; int min_tiles; };
+int pick_splits(const rdn_wgrad_desc* d, int base, int ntiles, const SplitRule& r) {
+  int s = d->splits > 0 ? d->splits : (r.target + (r.ceil ? base - 1 : 0)) / base;
+  const int maxs = (ntiles + r.min_tiles - 1) / r.min_tiles;
+  if (s > maxs) s = maxs;
+  return s < 1 ? 1 : s;
+}
 
 Plan plan(const rdn_wgrad_desc* d) {
   Plan p;
   p.bm = d->mdim <= 16 ? 16 : d->mdim <= 32 ? 32 : 64;
-  int ck = rdn_conv3_chunk_pow2(d->ndim, d->dtype == RDN_BF16 ? 64 : 32);
-  const int cap = d->dtype == RDN_BF16 ? (p.bm <= 32 ? 64 : 32) : 32;
-  while (ck > cap) ck >>= 1;
-  p.ck = ck;
-  p.rows = 0;
   if (d->dtype == RDN_BF16) {
-    // rows kernel: the widest channel group whose accumulators fit (BM x 9 CK per block)
-    // accumulator budget BM x CK <= 2560: two blocks per CU (measured r01: a
-    // 4096 budget at one block per CU, and 128-channel blocks, were slower)
-    const int maxacc = 2560, bm = p.bm;
+    // rows kernel: the widest channel group that divides ndim and fits ROWS_ACC (8 always
+    // fits, so ndim % 8 == 0 -- what rdn_conv_wgrad admits -- always finds one)
+    p.kind = ROWS;
+    p.ck = -1;
     static const int cands[] = {96, 80, 64, 48, 32, 16, 8};
     for (int c : cands)
-      if (d->ndim % c == 0 && c * bm <= maxacc) { p.ck = c; p.rows = 1; p.bm = bm; break; }
+      if (d->ndim % c == 0 && c * p.bm <= ROWS_ACC) { p.ck = c; break; }
+  } else {
+    p.kind = F32;
+    p.ck = rdn_conv3_chunk_pow2(d->ndim, 32);
   }
   p.chunks_rows = d->ndim / p.ck;   // the PReLU-gate fusion decision (rdn_wgrad_chunks) is made on these
-  p.glds = 0;
+  // The LDS-DMA pipelined kernel, one block per CU, takes the multi-chunk (level-1..3)
+  // bf16 launches without a gate; the single-chunk level-0/1 ones, where the rows plan
+  // reads the whole input pixel row in one channel group and the PReLU gate is fused,
+  // stay on the rows kernel.  (mdim >= 32: bm is 32 or 64 here.)
+  if (p.kind == ROWS && p.chunks_rows != 1 && !d->a_gate && d->mdim >= 32 && d->ndim % 32 == 0) {
+    p.kind = GLDS;
+    p.ck = d->ndim % 64 == 0 ? 64 : 32;
+    // the narrow level-1 layers (96 / 128 / 160 input channels): whole-row or half-row
+    // channel groups, so operand A (dYpre) is read 1-2 times instead of 2-5 (per-layer
+    // A/B, r03_v6: level-1 conv_1 / conv_3 weight gradients -10..-20 %, up_0 -28 %)
+    if (d->ndim <= 160) {
+      if (d->ndim % 96 == 0) p.ck = 96;
+      else if (d->ndim % 80 == 0) p.ck = 80;   // (128 as one group: 43 -> 45 us, kept at 2 x 64)
+    }
+  }
   p.tiles_x = (d->w + TW - 1) / TW;
   p.tiles_y = (d->h + TH - 1) / TH;
   p.ntiles = d->n * p.tiles_x * p.tiles_y;
-  // the LDS-DMA pipelined kernel (wgrad3_glds.hip), one block per CU: multi-chunk
-  // launches (no gate) and the single-chunk level-0/1 ones (gate fused)
-  if (p.rows && rdn_wgrad3_glds_pick(d, p.chunks_rows == 1, &p.bm, &p.ck)) {
-    p.glds = 1;
-    p.mtiles = (d->mdim + p.bm - 1) / p.bm;
-    p.chunks = d->ndim / p.ck;
-    const int base = p.mtiles * p.chunks;
-    // blocks per launch: 128 of the 256 CUs, leaving room beside the dgrad chain;
-    // step A/B (3 interleaved rounds, same box): 128: 1483, 192: 1506, 256: 1499,
-    // 512: 1416 img/s (past 256 the 1-per-CU blocks run in two waves); re-measured in
-    // r03 (profiles/r03_v10_wglds_blocks_ab.txt): 96: 1633, 128: 1698, 160: 1714,
-    // 192: 1714, 256: 1687; round 4, after the fused layers' work moved onto the
-    // compute stream (gate-out, batched reduce): 192: 1767 / 1991, 160: 1777 / 1997,
-    // 128: 1777 / 2011 img/s B16 / B32, then 128: 1764 / 1975, 112: 1759 / 1957,
-    // 96: 1730 / 1927 (profiles/r04_v28_wglds_blocks_ab.txt, r04_v29_*).  RDN_WGLDS_BLOCKS
-    static const int gtarget = rdn_env_int("RDN_WGLDS_BLOCKS", 128);
-    int s = d->splits > 0 ? d->splits : gtarget / base;
-    const int maxs = (p.ntiles + 1) / 2;                             // >= 2 tiles per block
-    if (s > maxs) s = maxs;
-    if (s < 1) s = 1;
-    p.tpb = (p.ntiles + s - 1) / s;
-    p.splits = s;
-    return p;
-  }
   p.mtiles = (d->mdim + p.bm - 1) / p.bm;
   p.chunks = d->ndim / p.ck;
-  const int base = p.mtiles * p.chunks;
-  // blocks per launch: one per CU.  The weight gradients run on the side stream
-  // beside the dgrad chain, where fewer, longer blocks (and half the split-K slab
+  // glds, blocks per launch: 128 of the 256 CUs, leaving room beside the dgrad chain;
+  // step A/B (3 interleaved rounds, same box): 128: 1483, 192: 1506, 256: 1499,
+  // 512: 1416 img/s (past 256 the 1-per-CU blocks run in two waves); re-measured in
+  // r03 (profiles/r03_v10_wglds_blocks_ab.txt): 96: 1633, 128: 1698, 160: 1714,
+  // 192: 1714, 256: 1687; round 4, after the fused layers' work moved onto the
+  // compute stream (gate-out, batched reduce): 192: 1767 / 1991, 160: 1777 / 1997,
+  // 128: 1777 / 2011 img/s B16 / B32, then 128: 1764 / 1975, 112: 1759 / 1957,
+  // 96: 1730 / 1927 (profiles/r04_v28_wglds_blocks_ab.txt, r04_v29_*).  RDN_WGLDS_BLOCKS
+  static const int gtarget = rdn_env_int("RDN_WGLDS_BLOCKS", 128);
+  // rows / f32, blocks per launch: one per CU.  The weight gradients run on the side
+  // stream beside the dgrad chain, where fewer, longer blocks (and half the split-K slab
   // bytes) won: whole step 1342 (512) -> 1362 (256) img/s; 128: 1165, 192: 1302,
   // 384: 1355, 1024: 1311
-  constexpr int target = 256;
-  int s = d->splits > 0 ? d->splits : (target + base - 1) / base;
-  const int maxs = (p.ntiles + 3) / 4;                             // >= 4 tiles per block
-  if (s > maxs) s = maxs;
-  if (s < 1) s = 1;
-  p.tpb = (p.ntiles + s - 1) / s;
-  p.splits = s;  // blocks past the last tile write zero slabs, so any s is exact
+  p.splits = pick_splits(d, p.mtiles * p.chunks, p.ntiles,
+                         p.kind == GLDS ? SplitRule{gtarget, false, 2} : SplitRule{256, true, 4});
+  p.tpb = (p.ntiles + p.splits - 1) / p.splits;
   return p;
 }
 
-template <typename T, int BM, int CK>
-int launch_w(const rdn_wgrad_desc* d, const Plan& p, hipStream_t st) {
+template <int BM, int CK>
+int launch_f32(const rdn_wgrad_desc* d, const Plan& p, hipStream_t st) {
   dim3 grid(p.mtiles, p.chunks, p.splits);
-  RDN_PROBE("wgrad3_halo_kernel<%s,%d,%d%s>", rdn_tname<T>(), BM, CK, d->a_gate ? ",gate" : "");
+  RDN_PROBE("wgrad3_halo_kernel<f32,%d,%d%s>", BM, CK, d->a_gate ? ",gate" : "");
   if (d->a_gate)
-    wgrad3_halo_kernel<T, BM, CK, true><<<grid, NT, 0, st>>>(*d, p.tiles_x, p.tiles_y, p.ntiles, p.tpb);
+    wgrad3_halo_kernel<BM, CK, true><<<grid, NT, 0, st>>>(*d, p.tiles_x, p.tiles_y, p.ntiles, p.tpb);
   else
-    wgrad3_halo_kernel<T, BM, CK, false><<<grid, NT, 0, st>>>(*d, p.tiles_x, p.tiles_y, p.ntiles, p.tpb);
+    wgrad3_halo_kernel<BM, CK, false><<<grid, NT, 0, st>>>(*d, p.tiles_x, p.tiles_y, p.ntiles, p.tpb);
   return rdn_check_launch("rdn_conv_wgrad(conv3)");
 }
 
 template <int BM, int CK>
 int launch_rows(const rdn_wgrad_desc* d, const Plan& p, hipStream_t st) {
-  if constexpr (CK * BM > 4096) {
+  if constexpr (CK * BM > ROWS_ACC) {
     rdn_set_error("rdn_conv_wgrad(conv3): rows kernel BM=%d CK=%d", BM, CK);
     return RDN_E_SHAPE;
   } else {
@@ -627,27 +613,23 @@ int launch_rows(const rdn_wgrad_desc* d, const Plan& p, hipStream_t st) {
 }
 
 template <int BM>
-int launch_rows_ck(const rdn_wgrad_desc* d, const Plan& p, hipStream_t st) {
-  switch (p.ck) {
-    case 96: return launch_rows<BM, 96>(d, p, st);
-    case 80: return launch_rows<BM, 80>(d, p, st);
-    case 64: return launch_rows<BM, 64>(d, p, st);
-    case 48: return launch_rows<BM, 48>(d, p, st);
-    case 32: return launch_rows<BM, 32>(d, p, st);
-    case 16: return launch_rows<BM, 16>(d, p, st);
-    case 8: return launch_rows<BM, 8>(d, p, st);
-  }
-  rdn_set_error("rdn_conv_wgrad(conv3): bad chunk %d", p.ck);
-  return RDN_E_SHAPE;
-}
-
-template <typename T, int BM>
-int launch_ck(const rdn_wgrad_desc* d, const Plan& p, hipStream_t st) {
-  switch (p.ck) {
-    case 64: if constexpr (sizeof(T) == 2 && BM <= 32) return launch_w<T, BM, 64>(d, p, st); break;
-    case 32: return launch_w<T, BM, 32>(d, p, st);
-    case 16: return launch_w<T, BM, 16>(d, p, st);
-    case 8: return launch_w<T, BM, 8>(d, p, st);
+int launch_bm(const rdn_wgrad_desc* d, const Plan& p, hipStream_t st) {
+  if (p.kind == ROWS) {
+    switch (p.ck) {
+      case 96: return launch_rows<BM, 96>(d, p, st);
+      case 80: return launch_rows<BM, 80>(d, p, st);
+      case 64: return launch_rows<BM, 64>(d, p, st);
+      case 48: return launch_rows<BM, 48>(d, p, st);
+      case 32: return launch_rows<BM, 32>(d, p, st);
+      case 16: return launch_rows<BM, 16>(d, p, st);
+      case 8: return launch_rows<BM, 8>(d, p, st);
+    }
+  } else {
+    switch (p.ck) {
+      case 32: return launch_f32<BM, 32>(d, p, st);
+      case 16: return launch_f32<BM, 16>(d, p, st);
+      case 8: return launch_f32<BM, 8>(d, p, st);
+    }
   }
   rdn_set_error("rdn_conv_wgrad(conv3): bad chunk %d", p.ck);
   return RDN_E_SHAPE;
@@ -661,20 +643,10 @@ int rdn_wgrad3_chunks(const rdn_wgrad_desc* d) { return plan(d).chunks_rows; }
 int rdn_wgrad3_launch(const rdn_wgrad_desc* d, hipStream_t st) {
   const Plan p = plan(d);
   if (p.ck <= 0) { rdn_set_error("rdn_conv_wgrad(conv3): ndim=%d", d->ndim); return RDN_E_SHAPE; }
-  if (p.glds)
+  if (p.kind == GLDS)
     return rdn_wgrad3_glds_launch(d, p.bm, p.ck, p.mtiles * p.chunks * p.splits, p.tiles_x, p.tiles_y, p.ntiles,
                                   p.tpb, st);
-  if (p.rows) {
-    if (p.bm == 16) return launch_rows_ck<16>(d, p, st);
-    if (p.bm == 32) return launch_rows_ck<32>(d, p, st);
-    return launch_rows_ck<64>(d, p, st);
-  }
-  if (d->dtype == RDN_BF16) {
-    if (p.bm == 16) return launch_ck<bf16, 16>(d, p, st);
-    if (p.bm == 32) return launch_ck<bf16, 32>(d, p, st);
-    return launch_ck<bf16, 64>(d, p, st);
-  }
-  if (p.bm == 16) return launch_ck<float, 16>(d, p, st);
-  if (p.bm == 32) return launch_ck<float, 32>(d, p, st);
-  return launch_ck<float, 64>(d, p, st);
+  if (p.bm == 16) return launch_bm<16>(d, p, st);
+  if (p.bm == 32) return launch_bm<32>(d, p, st);
+  return launch_bm<64>(d, p, st);
 }

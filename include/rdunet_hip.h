@@ -33,6 +33,7 @@
  *   rdn_charbonnier_fwd/bwd  charbonnier_loss/combined_loss, diffusion_RDUnet.py:57-65.
  *   rdn_sqnorm / rdn_clip_scale  torch.nn.utils.clip_grad_norm_, diffusion_RDUnet.py:113.
  *   rdn_adam_step     torch.optim.Adam / AdamW step, diffusion_RDUnet.py:264-268,127.
+ *   rdn_adadelta_step torch.optim.Adadelta step, diffusion_RDUnet.py:270-272,127.
  *   rdn_sampling_combine  the x_t update of improved_sampling, diffusion_RDUnet.py:45-49.
  *   rdn_synth_batch   CustomDataset/CustomSIDD_Dataset.__getitem__ + transforms
  *                     (dataset_creation/custom_dataset.py:64-100, SIDD_dataset.py:74-97).
@@ -349,6 +350,16 @@ int rdn_clip_scale(float* g, int64_t count, const float* coef, void* stream);
 int rdn_adam_step(float* p, const float* g, float* m, float* v, int64_t count,
                   double lr, double beta1, double beta2, double eps, double wd, int32_t decoupled,
                   int64_t step, const int64_t* step_dev, float grad_scale, void* stream);
+/* torch.optim.Adadelta step over flat fp32 buffers, one launch, torch's single-tensor
+   operation order:  g = g*grad_scale (+ weight_decay*p when weight_decay != 0);
+   sq = sq*rho + (1-rho)*g*g;  delta = sqrt(acc + eps) / sqrt(sq + eps) * g;
+   acc = acc*rho + (1-rho)*delta*delta;  p += -lr*delta.  rho, 1-rho, eps, -lr and
+   weight_decay are rounded to fp32 from double.  Nothing depends on a step count, so the
+   launch replays in a captured graph as it is.  Where p = g = 0 (the padding gaps of a
+   flat parameter buffer) delta is 0 and p stays 0.  count == 0 is a no-op; a null
+   pointer or count < 0 returns RDN_E_ARG before any launch. */
+int rdn_adadelta_step(float* p, const float* g, float* square_avg, float* acc_delta, int64_t count,
+                      double lr, double rho, double eps, double weight_decay, float grad_scale, void* stream);
 /* *counter += 1 on the device (one thread; stream-ordered) */
 int rdn_counter_inc(int64_t* counter, void* stream);
 /* buf[slot] = the device wall clock (constant rate, rdn_wall_clock_khz ticks per ms) when

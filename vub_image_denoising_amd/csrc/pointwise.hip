@@ -452,6 +452,55 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   }
 }
 
+// torch.optim.Adadelta single-tensor math (torch/optim/adadelta.py, _single_tensor_adadelta),
+// one rounding per torch op (its `self + alpha*x` kernels contract to one fma; nothing else
+// is contracted), every scalar rounded to fp32 from double:
+//   g = g*gs (+ wd*p) ; sq = sq*rho + (1-rho)*g*g
+//   delta = sqrt(acc + eps) / sqrt(sq + eps) * g ; acc = acc*rho + (1-rho)*delta*delta
+//   p += -lr * delta
+// Nothing depends on the step count: the launch is graph-replayable as it is.  In the
+// flat layout's padding gaps p = g = 0, so delta = 0 and p stays 0.
+struct AdadeltaScalars {
+  float rho, omr, eps, neg_lr, wd;
+};
+
+__device__ __forceinline__ void adadelta_elem(float& p, float g, float& sq, float& acc, const AdadeltaScalars& sc,
+                                              float gs) {
+#pragma clang fp contract(off)
+  g = g * gs;
+  if (sc.wd != 0.f) g = fmaf(sc.wd, p, g);        // grad.add(param, alpha=wd)
+  sq = sq * sc.rho;                               // mul_(rho)
+  sq = fmaf(sc.omr, g * g, sq);                   // addcmul_(g, g, value=1-rho): self + value*(t1*t2)
+  const float std_ = sqrtf(sq + sc.eps);
+  float d = sqrtf(acc + sc.eps);
+  d = d / std_;
+  d = d * g;
+  acc = acc * sc.rho;
+  acc = fmaf(sc.omr, d * d, acc);
+  p = fmaf(sc.neg_lr, d, p);                      // add_(delta, alpha=-lr)
+}
+
+__global__ __launch_bounds__(256) void adadelta_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ sq, float* __restrict__ acc, int64_t n,
+                                                       int64_t n4, AdadeltaScalars sc, float gs) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t i = tid; i < n4; i += stride) {    // n4 = n/4 when all four buffers are 16-byte aligned, else 0
+    f32x4 pv = ((f32x4*)p)[i], sv = ((f32x4*)sq)[i], av = ((f32x4*)acc)[i];
+    const f32x4 gv = ((const f32x4*)g)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pk = pv[k], sk = sv[k], ak = av[k];
+      adadelta_elem(pk, gv[k], sk, ak, sc, gs);
+      pv[k] = pk; sv[k] = sk; av[k] = ak;
+    }
+    ((f32x4*)p)[i] = pv;
+    ((f32x4*)sq)[i] = sv;
+    ((f32x4*)acc)[i] = av;
+  }
+  for (int64_t i = n4 * 4 + tid; i < n; i += stride) adadelta_elem(p[i], g[i], sq[i], acc[i], sc, gs);
+}
+
 __global__ void counter_inc_kernel(int64_t* c) { *c += 1; }
 
 // the device's constant-rate wall clock when this kernel starts, by one lane (vector
@@ -659,6 +708,25 @@ extern "C" int rdn_adam_step(float* p, const float* g, float* m, float* v, int64
   adam_kernel<<<grid_for(count, 256 * 4), 256, 0, RDN_STREAM>>>(p, g, m, v, count, sc, step_dev, lr, beta1, beta2, eps,
                                                                wd, decoupled, grad_scale);
   return rdn_check_launch("rdn_adam_step");
+}
+
+extern "C" int rdn_adadelta_step(float* p, const float* g, float* square_avg, float* acc_delta, int64_t count,
+                                 double lr, double rho, double eps, double weight_decay, float grad_scale,
+                                 void* stream) {
+  if (!p || !g || !square_avg || !acc_delta) { rdn_set_error("rdn_adadelta_step: null pointer"); return RDN_E_ARG; }
+  if (count < 0) { rdn_set_error("rdn_adadelta_step: count %lld < 0", (long long)count); return RDN_E_ARG; }
+  if (count == 0) return RDN_OK;
+  AdadeltaScalars sc;
+  sc.rho = (float)rho;
+  sc.omr = (float)(1.0 - rho);
+  sc.eps = (float)eps;
+  sc.neg_lr = (float)(-lr);
+  sc.wd = (float)weight_decay;
+  const bool aligned = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)square_avg | (uintptr_t)acc_delta) & 15) == 0;
+  const int64_t n4 = aligned ? count / 4 : 0;
+  adadelta_kernel<<<grid_for(aligned ? n4 + 3 : count, 256 * 4), 256, 0, RDN_STREAM>>>(p, g, square_avg, acc_delta, count,
+                                                                                     n4, sc, grad_scale);
+  return rdn_check_launch("rdn_adadelta_step");
 }
 
 extern "C" int rdn_counter_inc(int64_t* counter, void* stream) {

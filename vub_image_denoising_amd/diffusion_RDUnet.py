@@ -168,16 +168,19 @@ def train_step_checkpointed(model, clean_images, noisy_images, optimizer, accumu
 
 def train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir,
                              distribution_choice='uniform', num_epochs=10, start_epoch=0, accumulation_steps=4,
-                             clip_value=1.0, log_every=1, accumulation='reference', loss_weights=None):
+                             clip_value=1.0, log_every=1, accumulation='reference', loss_weights=None, *,
+                             captured=False):
     """diffusion_RDUnet.py:117-178: epochs of train steps with the reference's
     every-``accumulation_steps`` optimizer step, one-batch improved_sampling
     validation, scheduler step and a checkpoint dict per epoch.  ``log_every``
     > 1 rate-limits the per-batch ``loss.item()`` host sync; ``accumulation``
     selects the reference's update rule or the fixed one (see run_epochs);
-    ``loss_weights`` the loss mix of the train steps and the validation loss."""
+    ``loss_weights`` the loss mix of the train steps and the validation loss;
+    ``captured`` replays every batch as one hipGraph (fused optimizers only)."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir, distribution_choice,
                num_epochs, start_epoch, accumulation_steps, clip_value, log_every,
-               sample=lambda m, x: m.improved_sampling(x), accumulation=accumulation, loss_weights=loss_weights)
+               sample=lambda m, x: m.improved_sampling(x), accumulation=accumulation, loss_weights=loss_weights,
+               captured=captured)
 
 
 ACCUMULATION_MODES = ("reference", "fixed")
@@ -185,7 +188,7 @@ ACCUMULATION_MODES = ("reference", "fixed")
 
 def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir, distribution_choice,
                num_epochs, start_epoch, accumulation_steps, clip_value, log_every, sample, accumulation='reference',
-               skip_discarded=True, loss_weights=None):
+               skip_discarded=True, loss_weights=None, captured=False):
     """The epoch loop shared by the three reference trainers (diffusion_RDUnet.py:117-178,
     main_diffusion_RDUnet.py:275-336, diffusion_RDUnet_direct.py:266-327); they
     differ only in the validation sampler and the checkpoint directory.
@@ -202,19 +205,43 @@ def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, ou
     ``skip_discarded=False`` runs the discarded backward passes anyway (the
     reference's literal work; tests compare the two bit for bit).
     ``loss_weights``: the ``(mse, charbonnier, ssim)`` weights of the train and
-    validation loss, None for the reference's (0, 1, 0)."""
+    validation loss, None for the reference's (0, 1, 0).
+
+    ``captured=True`` replays each batch as one hipGraph (train_graph.TrainStepGraphs,
+    one graph per batch shape and kind, kept on the model) instead of issuing it from
+    Python: in the reference mode the ``accumulation_steps``-th batch replays the whole
+    step (update included), a logged other batch the forward + loss, and an unlogged one
+    only draws its t; in the fixed mode the batches replay backward passes that add into
+    a flat accumulator, the ``accumulation_steps``-th with clip and update.  The update
+    is inside the graph, so the optimizer must be a fused one
+    (``make_optimizer(..., fused=True)``); the parameters, optimizer state and logged
+    losses are the eager loop's bit for bit (``skip_discarded`` has no captured form)."""
     if accumulation not in ACCUMULATION_MODES:
         raise ValueError(f"accumulation must be one of {ACCUMULATION_MODES}, got {accumulation!r}")
+    graphs = None
+    if captured:
+        from . import train_graph
+        graphs = train_graph.trainer_graphs(model, optimizer, distribution_choice, clip_value, loss_weights)
     dev = next(model.parameters()).device
     for epoch in range(start_epoch, num_epochs):
         model.train()
         optimizer.zero_grad()
+        if captured:
+            train_graph.clear_accumulator(model)   # a leftover partial group is discarded
         n_batches = len(train_loader) if hasattr(train_loader, "__len__") else 0
         for batch_idx, (noisy_images, clean_images) in enumerate(train_loader):
             noisy_images, clean_images = noisy_images.to(dev), clean_images.to(dev)
             step_now = (batch_idx + 1) % accumulation_steps == 0
             log_now = batch_idx % log_every == 0
-            if accumulation == 'fixed':
+            if captured:
+                if accumulation == 'fixed':
+                    loss_t = graphs(clean_images, noisy_images, kind='accum_step' if step_now else 'accum')
+                elif step_now or log_now:
+                    loss_t = graphs(clean_images, noisy_images, kind='step' if step_now else 'loss')
+                else:
+                    loss_t = forward_step_device(model, clean_images, noisy_images, distribution_choice,
+                                                 need_loss=False)
+            elif accumulation == 'fixed':
                 loss_t = train_step_device(model, clean_images, noisy_images, optimizer, distribution_choice,
                                            clip_value, zero_grad=False, clip=False, loss_weights=loss_weights)
                 if step_now:
@@ -225,7 +252,7 @@ def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, ou
             else:
                 loss_t = forward_step_device(model, clean_images, noisy_images, distribution_choice,
                                              need_loss=log_now, loss_weights=loss_weights)
-            if step_now:
+            if step_now and not captured:
                 optimizer.step()
                 optimizer.zero_grad()
             if log_now:
@@ -278,7 +305,16 @@ def load_checkpoint(model, optimizer, scheduler, checkpoint_path):
 
 
 def load_data(args):
-    """diffusion_RDUnet.py:222-228 dispatch on ``args.dataset_choice``."""
+    """diffusion_RDUnet.py:222-228 dispatch on ``args.dataset_choice``;
+    ``args.data_pipeline == 'gpu'``: the device-side loaders of ``synth`` over the same
+    folders (no worker processes)."""
+    if getattr(args, "data_pipeline", "pil") == 'gpu':
+        from . import synth
+        kw = dict(batch_size=args.batch_size, augment=args.augment, dataset_percentage=args.dataset_percentage,
+                  validation_split=args.validation_split, use_rgb=True)
+        if args.dataset_choice == 'DIV2K':
+            return synth.load_data_gpu('dataset/DIV2K_train_HR.nosync', **kw)
+        return synth.load_sidd_data_gpu('dataset/SIDD_dataset.nosync/SIDD_Medium_Srgb', **kw)
     from .data_loader import load_data as load_div2k_data, load_sidd_data
     if args.dataset_choice == 'DIV2K':
         return load_div2k_data('dataset/DIV2K_train_HR.nosync', batch_size=args.batch_size, augment=args.augment,
@@ -289,16 +325,22 @@ def load_data(args):
                           validation_split=args.validation_split, use_rgb=True, num_workers=args.num_workers)
 
 
-def make_optimizer(args, params):
-    """diffusion_RDUnet.py:264-276 choices."""
+def make_optimizer(args, params, fused=False):
+    """diffusion_RDUnet.py:264-276 choices; ``fused=True``: the one-launch optimizers of
+    ``optim`` with the same hyperparameters (what ``captured=True`` training needs)."""
+    if fused:
+        from . import optim as fused_optim
+        adam, adamw, adadelta = fused_optim.FusedAdam, fused_optim.FusedAdamW, fused_optim.FusedAdadelta
+    else:
+        adam, adamw, adadelta = optim.Adam, optim.AdamW, optim.Adadelta
     if args.optimizer_choice == 'adam':
-        optimizer = optim.Adam(params, lr=args.lr, betas=(0.9, 0.999))
+        optimizer = adam(params, lr=args.lr, betas=(0.9, 0.999))
         scheduler = CosineAnnealingLR(optimizer, T_max=10)
     elif args.optimizer_choice == 'adamw':
-        optimizer = optim.AdamW(params, lr=args.lr, weight_decay=args.weight_decay)
+        optimizer = adamw(params, lr=args.lr, weight_decay=args.weight_decay)
         scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=3, gamma=0.5)
     else:
-        optimizer = optim.Adadelta(params, lr=args.lr)
+        optimizer = adadelta(params, lr=args.lr)
         scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=3, gamma=0.5)
     return optimizer, scheduler
 
@@ -316,13 +358,14 @@ def train(args, train_loader=None, val_loader=None):
     unet.set_compute_dtype(getattr(args, "dtype", "fp32"))
     model = DiffusionModel(unet, timesteps=args.timesteps).to(device)
     unet.apply(init_weights())
-    optimizer, scheduler = make_optimizer(args, model.parameters())
+    captured = getattr(args, "step_mode", "eager") == 'graph'
+    optimizer, scheduler = make_optimizer(args, model.parameters(), fused=captured)
     start_epoch = load_checkpoint(model, optimizer, scheduler, args.checkpoint_path)
     train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, args.output_dir,
                              args.distribution_choice, num_epochs=args.num_epochs, start_epoch=start_epoch,
                              accumulation=getattr(args, "accumulation", "reference"),
                              loss_weights=(getattr(args, "mse_weight", 0.0), getattr(args, "charbonnier_weight", 1.0),
-                                           getattr(args, "ssim_weight", 0.0)))
+                                           getattr(args, "ssim_weight", 0.0)), captured=captured)
     final_model_path = os.path.join(args.output_dir, "diffusion_RDUNet_model_checkpointed_final.pth")
     torch.save(model.state_dict(), final_model_path)
     print(f"Final model saved at {final_model_path}")
@@ -331,8 +374,8 @@ def train(args, train_loader=None, val_loader=None):
 
 
 def build_parser():
-    """diffusion_RDUnet.py:293-309, plus --dtype, --accumulation and the three
-    weights of ``combined_loss`` (:60)."""
+    """diffusion_RDUnet.py:293-309, plus --dtype, --accumulation, the three
+    weights of ``combined_loss`` (:60), --step_mode and --data_pipeline."""
     parser = argparse.ArgumentParser(description="Train a diffusion model with optional optimizer and scheduler choice.")
     parser.add_argument('--dataset_choice', type=str, default='SIDD', choices=['DIV2K', 'SIDD'])
     parser.add_argument('--checkpoint_path', type=str, default=None)
@@ -357,6 +400,10 @@ def build_parser():
     parser.add_argument('--mse_weight', type=float, default=0.0)
     parser.add_argument('--charbonnier_weight', type=float, default=1.0)
     parser.add_argument('--ssim_weight', type=float, default=0.0, help="weight of 1 - SSIM (gaussian 11x11)")
+    parser.add_argument('--step_mode', type=str, default='eager', choices=['eager', 'graph'],
+                        help="graph: fused optimizer, every batch replayed as one captured hipGraph")
+    parser.add_argument('--data_pipeline', type=str, default='pil', choices=['pil', 'gpu'],
+                        help="gpu: patches cut and augmented on the device (synth loaders), no worker processes")
     return parser
 
 

@@ -23,9 +23,9 @@ class DiffusionModel(_base.DiffusionModel):
         return self.direct_sampling(noisy_step_image)
 
 
-def make_training_objects(base_filters=32, lr=2e-4, dev=None):
+def make_training_objects(base_filters=32, lr=2e-4, dev=None, fused=False):
     """diffusion_RDUnet_direct.py:219-222 (same objects as main_diffusion_RDUnet.py:228-231)."""
-    return _main.make_training_objects(base_filters, lr, dev, model_cls=DiffusionModel)
+    return _main.make_training_objects(base_filters, lr, dev, model_cls=DiffusionModel, fused=fused)
 
 
 def _sample(model, x):
@@ -34,8 +34,8 @@ def _sample(model, x):
 
 def train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, num_epochs=10,
                              start_epoch=0, accumulation_steps=4, clip_value=1.0, *, accumulation='reference',
-                             loss_weights=None):
-    """diffusion_RDUnet_direct.py:266-327 (validation with direct_sampling)."""
+                             loss_weights=None, captured=False):
+    """diffusion_RDUnet_direct.py:266-327 (validation with direct_sampling; ``captured``: see run_epochs)."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, CHECKPOINT_DIR, 'uniform', num_epochs,
                start_epoch, accumulation_steps, clip_value, 1, sample=_sample, accumulation=accumulation,
-               loss_weights=loss_weights)
+               loss_weights=loss_weights, captured=captured)

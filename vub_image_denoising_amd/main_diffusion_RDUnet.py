@@ -31,13 +31,18 @@ from .Unet_model import (DenoisingBlock, DownsampleBlock, InputBlock, OutputBloc
 CHECKPOINT_DIR = "checkpoints"
 
 
-def make_training_objects(base_filters=32, lr=2e-4, dev=None, model_cls=None):
+def make_training_objects(base_filters=32, lr=2e-4, dev=None, model_cls=None, fused=False):
     """main_diffusion_RDUnet.py:228-231: RDUNet_T(32), DiffusionModel, Adam(lr, (0.9, 0.999)),
-    CosineAnnealingLR(T_max=10)."""
+    CosineAnnealingLR(T_max=10).  ``fused=True``: optim.FusedAdam with the same
+    hyperparameters (for ``train_model_checkpointed(..., captured=True)``)."""
     dev = dev or device
     unet = RDUNet_T(base_filters=base_filters).to(dev)
     model = (model_cls or DiffusionModel)(unet).to(dev)
-    optimizer = optim.Adam(model.parameters(), lr=lr, betas=(0.9, 0.999))
+    if fused:
+        from .optim import FusedAdam
+        optimizer = FusedAdam(model.parameters(), lr=lr, betas=(0.9, 0.999))
+    else:
+        optimizer = optim.Adam(model.parameters(), lr=lr, betas=(0.9, 0.999))
     scheduler = CosineAnnealingLR(optimizer, T_max=10)
     return unet, model, optimizer, scheduler
 
@@ -55,11 +60,11 @@ def _sample(model, x):
 
 def train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, num_epochs=10,
                              start_epoch=0, accumulation_steps=4, clip_value=1.0, *, accumulation='reference',
-                             loss_weights=None):
-    """main_diffusion_RDUnet.py:275-336."""
+                             loss_weights=None, captured=False):
+    """main_diffusion_RDUnet.py:275-336 (``captured``: see run_epochs)."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, CHECKPOINT_DIR, 'uniform', num_epochs,
                start_epoch, accumulation_steps, clip_value, 1, sample=_sample, accumulation=accumulation,
-               loss_weights=loss_weights)
+               loss_weights=loss_weights, captured=captured)
 
 
 def load_checkpoint(model, optimizer, scheduler, checkpoint_path):

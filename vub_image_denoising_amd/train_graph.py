@@ -23,6 +23,18 @@ What makes the step capturable:
 
 The graph owns the parameters' ``.grad`` (views of the flat gradient buffer its
 backward writes); an eager step in between is allowed and does not disturb it.
+
+Besides the full step (``kind='step'``) a graph can capture the other batches the
+trainers issue (diffusion_RDUnet.run_epochs): ``'loss'`` (the t draw, forward and
+loss of a batch whose gradient the reference discards, forward_step_device),
+``'accum'`` (t draw, forward, loss, backward, the gradient added into the model's
+flat accumulator) and ``'accum_step'`` (the same, then clip and update on the
+accumulated gradient and the accumulator cleared): the fixed accumulation mode.
+The accumulator is one flat fp32 buffer of the gradient layout per model
+(``grad_accumulator``), shared by the graphs of every shape; each backward writes
+its own flat buffer and ONE flat ``add_`` folds it in (eager accumulation is 207
+per-tensor adds of the same elements: the same bits).  After an accumulate replay the
+parameters' ``.grad`` are views of the accumulator, as after eager accumulation.
 """
 from __future__ import annotations
 
@@ -30,10 +42,38 @@ import os
 
 import torch
 
-from .diffusion_RDUnet import sample_biased, train_step_device
+from .diffusion_RDUnet import forward_step_device, sample_biased, train_step_device
 from .engine import find_flat
-from .functional import loss_weights_or_default
-from .optim import FusedAdam
+from .functional import clip_grad_norm_, loss_weights_or_default
+
+KINDS = ("step", "loss", "accum", "accum_step")
+_FUSED_SURFACE = ("graph_buffers", "graph_key", "use_device_step", "set_step", "_replayed")
+
+
+def is_fused(optimizer) -> bool:
+    """The optimizer has what a captured step needs (optim.FusedFlatOptimizer's surface)."""
+    return all(hasattr(optimizer, a) for a in _FUSED_SURFACE)
+
+
+def grad_accumulator(fp):
+    """The model's flat gradient accumulator (created on first use) and its
+    per-parameter views.  It is a member of the gradient buffer pool, so ``.grad``
+    tensors that are its views count as flat (clip and the fused update run on it as
+    single launches); the views held here keep a backward from taking it as scratch."""
+    acc = getattr(fp, "_accum", None)
+    if acc is None:
+        acc = fp._accum = torch.zeros(fp.numel, dtype=torch.float32, device=fp.device)
+        fp._gpool.append(acc)
+        fp._accum_views = fp.grad_views(acc)
+    return acc, fp._accum_views
+
+
+def clear_accumulator(model):
+    """Discard a partial accumulation group (the trainers' ``optimizer.zero_grad()`` at the
+    start of an epoch)."""
+    fp = getattr(model.unet, "_rdn_flat", None)
+    if fp is not None and getattr(fp, "_accum", None) is not None:
+        fp._accum.zero_()
 
 
 class GraphCaptureUnsafe(RuntimeError):
@@ -87,9 +127,15 @@ def _node_count(g):
 
 class TrainStepGraph:
     def __init__(self, model, optimizer, shape, distribution_choice='uniform', clip_value=1.0, t_input=False,
-                 warmup=2, loss_weights=None):
-        if not isinstance(optimizer, FusedAdam):
-            raise TypeError("TrainStepGraph needs the fused optimizer (optim.FusedAdam / FusedAdamW)")
+                 warmup=2, loss_weights=None, kind='step'):
+        if not is_fused(optimizer):
+            raise TypeError("TrainStepGraph needs a fused optimizer (optim.FusedAdam / FusedAdamW / FusedAdadelta)")
+        if kind not in KINDS:
+            raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
+        sync = getattr(getattr(model.unet, "_rdn_flat", None), "grad_sync", None)
+        if kind != 'step' and sync is not None and sync.world > 1:
+            raise NotImplementedError(f"data-parallel capture of kind {kind!r} is not implemented (only 'step')")
+        self.kind = kind
         self.model, self.opt = model, optimizer
         self.dist, self.clip = distribution_choice, clip_value
         self.loss_weights = loss_weights    # (mse, charbonnier, ssim) of combined_loss; None: (0, 1, 0)
@@ -108,19 +154,36 @@ class TrainStepGraph:
         weights, the compute dtype, and the addresses of the buffers the optimizer
         updates (a rebound optimizer or a re-flattened model re-captures instead of
         replaying onto freed memory)."""
-        g = self.opt.param_groups[0]
-        o = self.opt
-        ptrs = tuple(0 if b is None else b.data_ptr()
-                     for b in (getattr(o, "_m", None), getattr(o, "_v", None), o._step_dev,
-                               None if o._fp is None else o._fp.flat))
-        return (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), float(self.clip),
-                float(self.opt.grad_scale), self.model.unet.compute_dtype, ptrs,
+        return (self.opt.graph_key(), float(self.clip), self.model.unet.compute_dtype,
                 loss_weights_or_default(self.loss_weights))
 
     def _body(self):
+        if self.kind == 'loss':
+            return forward_step_device(self.model, self.clean, self.noisy, self.dist, t=self.t, need_loss=True,
+                                       loss_weights=self.loss_weights)
+        if self.kind == 'step':
+            loss = train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t,
+                                     loss_weights=self.loss_weights)
+            self.opt.step()
+            return loss
+        # 'accum' / 'accum_step': this backward's gradient lands in a flat buffer of its
+        # own (the parameters' .grad are dropped first), one flat add folds it into the
+        # accumulator, and .grad become the accumulator's views, which clip and the
+        # update then see as the flat gradient
         loss = train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t,
-                                 loss_weights=self.loss_weights)
-        self.opt.step()
+                                 clip=False, loss_weights=self.loss_weights)
+        params = list(self.model.parameters())
+        fp = find_flat(params)
+        if fp is None:
+            raise RuntimeError("TrainStepGraph: the backward did not leave flat gradient views")
+        acc, views = grad_accumulator(fp)
+        acc.add_(fp.gflat)
+        for p, v in zip(fp.params, views):
+            p.grad = v
+        if self.kind == 'accum_step':
+            clip_grad_norm_(params, self.clip, want_norm=False)
+            self.opt.step()
+            acc.zero_()
         return loss
 
     def _build(self, warmup):
@@ -135,15 +198,16 @@ class TrainStepGraph:
                                   loss_weights=self.loss_weights)
             self.opt.use_device_step()
             fp, opt = self.opt._fp, self.opt
-            snap = (fp.flat.clone(), opt._m.clone(), opt._v.clone(), opt._step)
+            state = [fp.flat] + opt.graph_buffers()
+            if self.kind in ('accum', 'accum_step'):
+                state.append(grad_accumulator(fp)[0])   # may hold a partial group: kept
+            snap = [b.clone() for b in state]
+            step0 = opt._step
             for _ in range(max(1, warmup)):
                 self._body()
-            fp.flat.copy_(snap[0])
-            opt._m.copy_(snap[1])
-            opt._v.copy_(snap[2])
-            opt._step = snap[3]
-            opt._steps.fill_(opt._step)
-            opt._step_dev.fill_(opt._step)
+            for b, s in zip(state, snap):
+                b.copy_(s)
+            opt.set_step(step0)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize(self.dev)
         _drain_collectives(fp)
@@ -159,8 +223,7 @@ class TrainStepGraph:
         self.graph = g
         self._captured = self._hyper()
         # capture ran nothing: undo its host-side effects (step count, pack keys)
-        opt._step = snap[3]
-        opt._steps.fill_(opt._step)
+        opt.set_step(step0, device=False)
         fp.generation += 1
         torch.cuda.set_rng_state(rng, self.dev)
 
@@ -181,17 +244,19 @@ class TrainStepGraph:
         elif t is not None:
             raise ValueError("this graph draws t itself (build it with t_input=True to pass t)")
         self.graph.replay()
-        self.opt._replayed()
+        if self.kind in ('step', 'accum_step'):
+            self.opt._replayed()
         return self.loss
 
 
 class TrainStepGraphs:
-    """One captured train step per input shape (config 5's mixed 128/256 patch
-    stream, synth.MixedPatchLoader): a batch of a new shape captures its own
+    """One captured train step per input shape and kind (config 5's mixed 128/256
+    patch stream, synth.MixedPatchLoader; the trainers' step / loss / accumulate
+    batches): a batch of a new (shape, kind) captures its own
     TrainStepGraph (its own engine, activations and graph); the graphs share the
-    model's flat parameters, gradient buffer and the optimizer's state (Adam moments
-    and the device step counter), and replays run one after another on the stream,
-    so the alternation is the same sequence of steps as eager training."""
+    model's flat parameters, gradient buffer and accumulator and the optimizer's state
+    (moments and the device step counter), and replays run one after another on the
+    stream, so the alternation is the same sequence of steps as eager training."""
 
     def __init__(self, model, optimizer, distribution_choice='uniform', clip_value=1.0, t_input=False, warmup=2,
                  loss_weights=None):
@@ -201,10 +266,25 @@ class TrainStepGraphs:
         self.graphs = {}
         self.captures = 0
 
-    def __call__(self, clean_images, noisy_images, t=None):
-        shape = tuple(clean_images.shape)
-        g = self.graphs.get(shape)
+    def __call__(self, clean_images, noisy_images, t=None, kind='step'):
+        key = (tuple(clean_images.shape), kind)
+        g = self.graphs.get(key)
         if g is None:
-            g = self.graphs[shape] = TrainStepGraph(self.model, self.opt, shape, **self.kw)
+            g = self.graphs[key] = TrainStepGraph(self.model, self.opt, key[0], kind=kind, **self.kw)
             self.captures += 1
         return g(clean_images, noisy_images, t)
+
+
+def trainer_graphs(model, optimizer, distribution_choice='uniform', clip_value=1.0, loss_weights=None):
+    """The TrainStepGraphs of a trainer (run_epochs(captured=True)), kept on the model:
+    a later call with the same optimizer and settings replays what an earlier one
+    captured."""
+    if not is_fused(optimizer):
+        raise TypeError("captured training needs a fused optimizer: build it with make_optimizer(..., fused=True) "
+                        f"(optim.FusedAdam / FusedAdamW / FusedAdadelta), got {type(optimizer).__name__}")
+    key = (distribution_choice, float(clip_value), loss_weights_or_default(loss_weights))
+    table = model.__dict__.setdefault("_rdn_train_graphs", {})
+    g = table.get(key)
+    if g is None or g.opt is not optimizer:
+        g = table[key] = TrainStepGraphs(model, optimizer, distribution_choice, clip_value, loss_weights=loss_weights)
+    return g

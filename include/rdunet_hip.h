@@ -31,6 +31,7 @@
  *   rdn_interp        x = a*noisy + (1-a)*clean, diffusion_RDUnet.py:90-100, :33-36.
  *   rdn_pack_input    torch.cat((inputs, t.expand(...)), 1), Unet_model.py:135-136.
  *   rdn_charbonnier_fwd/bwd  charbonnier_loss/combined_loss, diffusion_RDUnet.py:57-65.
+ *   rdn_l1_fwd/bwd    nn.L1Loss of the plain RDUNet baseline's trainer, UNet/RDUNet_model.py:201-215.
  *   rdn_sqnorm / rdn_clip_scale  torch.nn.utils.clip_grad_norm_, diffusion_RDUnet.py:113.
  *   rdn_adam_step     torch.optim.Adam / AdamW step, diffusion_RDUnet.py:264-268,127.
  *   rdn_adadelta_step torch.optim.Adadelta step, diffusion_RDUnet.py:270-272,127.
@@ -310,6 +311,17 @@ int rdn_charbonnier_fwd(const float* pred, const float* target, int64_t count, f
 /* dpred = gout[0] * (wc * d/sqrt(d^2+eps^2) + wm * 2d) / count */
 int rdn_charbonnier_bwd(const float* pred, const float* target, int64_t count, float eps,
                         float wc, float wm, const float* gout, float* dpred, void* stream);
+
+/* L1 (nn.L1Loss, mean reduction) over `count` fp32 elements, any count > 0.
+   ws >= rdn_reduce_workspace_size(count).  out[0] = mean|pred - target|: per-block fp32
+   partials in a fixed order, then one block summing them in double (no atomics: the same
+   input gives the same bits).  128-bit accesses when every pointer is 16-byte aligned,
+   element accesses otherwise and for the count % 4 tail. */
+int rdn_l1_fwd(const float* pred, const float* target, int64_t count, float* ws, float* out,
+               void* stream);
+/* dpred[i] = (gout[0] / (float)count) * sgn(pred[i] - target[i]), sgn(0) = 0 (torch.sign) */
+int rdn_l1_bwd(const float* pred, const float* target, int64_t count, const float* gout,
+               float* dpred, void* stream);
 
 /* SSIM term of combined_loss (diffusion_RDUnet.py:60-65): pytorch_msssim.ssim (v1.0.0;
    gaussian 11, sigma 1.5, valid, size_average) of fp32 NCHW x, y.  ws:

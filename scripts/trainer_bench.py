@@ -17,7 +17,13 @@ batch handed to the loop until the device has finished the last one (what the ba
 cost), and ``epoch`` for the whole call (adds the epoch's checkpoint write).  The
 per-batch ``print`` of the loop goes to an in-memory sink.
 
+``--model baseline`` times the plain RDUNet baseline's trainer instead
+(RDUNet_model.train_model: L1 loss, its one accumulation rule, RDUNet(base_filters)),
+the same variants.
+
     python scripts/trainer_bench.py --out profiles/trainer_graph_bench.json
+    python scripts/trainer_bench.py --model baseline --base-filters 128 --dtype fp32 --batch-sizes 16 \
+        --batches 16 --warmup-batches 8 --variants b c d --out profiles/baseline_trainer_bench_f128_fp32.json
 """
 import argparse
 import contextlib
@@ -74,9 +80,13 @@ def make_variant(name, args):
     from vub_image_denoising_amd.optim import FusedAdamW
     fused, captured, log_every = VARIANTS[name]
     torch.manual_seed(0)
-    unet = vm.RDUNet_T(base_filters=args.base_filters).cuda()
-    unet.set_compute_dtype(args.dtype)
-    model = DiffusionModel(unet, timesteps=20).cuda()
+    if args.model == "baseline":
+        model = vm.RDUNet(base_filters=args.base_filters).cuda()
+        model.set_compute_dtype(args.dtype)
+    else:
+        unet = vm.RDUNet_T(base_filters=args.base_filters).cuda()
+        unet.set_compute_dtype(args.dtype)
+        model = DiffusionModel(unet, timesteps=20).cuda()
     cls = FusedAdamW if fused else torch.optim.AdamW
     opt = cls(model.parameters(), lr=1e-4, weight_decay=1e-4)
     return dict(name=name, model=model, opt=opt, captured=captured, log_every=log_every, loop=[], epoch=[])
@@ -84,17 +94,22 @@ def make_variant(name, args):
 
 def run_pass(v, loader, mode, outdir):
     from vub_image_denoising_amd.diffusion_RDUnet import run_epochs
+    from vub_image_denoising_amd.RDUNet_model import train_model
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     with contextlib.redirect_stdout(io.StringIO()):
-        run_epochs(v["model"], loader, None, v["opt"], None, None, outdir, 'uniform', 1, 0, 4, 1.0, v["log_every"],
-                   sample=None, accumulation=mode, captured=v["captured"])
+        if mode == "baseline":
+            train_model(v["model"], loader, None, v["opt"], None, None, outdir, 1, accumulation_steps=4,
+                        clip_value=1.0, log_every=v["log_every"], captured=v["captured"])
+        else:
+            run_epochs(v["model"], loader, None, v["opt"], None, None, outdir, 'uniform', 1, 0, 4, 1.0, v["log_every"],
+                       sample=None, accumulation=mode, captured=v["captured"])
     torch.cuda.synchronize()
     return loader.t1 - loader.t0, time.perf_counter() - t0
 
 
 def bench_config(batch, mode, args, outdir):
-    variants = [make_variant(n, args) for n in VARIANTS]
+    variants = [make_variant(n, args) for n in VARIANTS if n[0] in args.variants]
     warm = DeviceBatches(args.warmup_batches, batch, args.size)
     loader = DeviceBatches(args.batches, batch, args.size)
     for v in variants:
@@ -118,7 +133,7 @@ def bench_config(batch, mode, args, outdir):
               f"{row['img_per_s']:7.1f} img/s  (passes {row['loop_s_passes']}, whole call {epoch:.3f} s)", flush=True)
     base = rows[0]["loop_ms_per_batch"]
     for r in rows:
-        r["speedup_vs_a"] = base / r["loop_ms_per_batch"]
+        r["speedup_vs_" + rows[0]["variant"][0]] = base / r["loop_ms_per_batch"]
     del variants
     torch.cuda.empty_cache()
     return rows
@@ -134,6 +149,9 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--base-filters", type=int, default=32)
     ap.add_argument("--dtype", default="bf16", choices=["fp32", "bf16"])
+    ap.add_argument("--model", default="diffusion", choices=["diffusion", "baseline"],
+                    help="baseline: RDUNet_model.train_model on a plain RDUNet (--modes is not used)")
+    ap.add_argument("--variants", nargs="+", default=["a", "b", "c", "d"], choices=["a", "b", "c", "d"])
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "trainer_graph_bench.json"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -143,9 +161,10 @@ def main():
     rows = []
     with tempfile.TemporaryDirectory() as outdir:
         for batch in args.batch_sizes:
-            for mode in args.modes:
+            for mode in (["baseline"] if args.model == "baseline" else args.modes):
                 rows += bench_config(batch, mode, args, outdir)
-    result = dict(what="run_epochs, one epoch, val_loader=None; median of interleaved passes",
+    what = "RDUNet_model.train_model" if args.model == "baseline" else "run_epochs"
+    result = dict(what=what + ", one epoch, val_loader=None; median of interleaved passes", model=args.model,
                   device=torch.cuda.get_device_name(0), torch=torch.__version__, batches=args.batches,
                   passes=args.passes, size=args.size, base_filters=args.base_filters, dtype=args.dtype,
                   accumulation_steps=4, rows=rows)

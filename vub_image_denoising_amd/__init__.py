@@ -4,7 +4,8 @@ diffusion-RDUNet denoising hot path of pierregab/VUB_Image_denoising.
 Drop-in modules (same names/signatures as the reference):
   Unet_model        RDUNet_T, InputBlock, OutputBlock, DenoisingBlock,
                     DownsampleBlock, UpsampleBlock, init_weights
-  RDUNet_model      RDUNet
+  RDUNet_model      RDUNet and the baseline's trainer (train_step, train_model,
+                    load_checkpoint)
   diffusion_RDUnet  DiffusionModel, charbonnier_loss, combined_loss,
                     train_step_checkpointed, train_model_checkpointed, ...
   data_loader       load_data (DIV2K-style folder loader, synthetic loader)

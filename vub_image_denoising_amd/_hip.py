@@ -123,7 +123,9 @@ SIGNATURES = {
     "rdn_reduce_workspace_size": (_i64, [_i64]),
     "rdn_charbonnier_fwd": (_i32, [_vp, _vp, _i64, _f32, _vp, _vp, _vp]),
     "rdn_charbonnier_bwd": (_i32, [_vp, _vp, _i64, _f32, _f32, _f32, _vp, _vp, _vp]),
-    "rdn_ssim_workspace_size": (_i64, [_i32, _i32, _i32, _i32]),
+    "rdn_l1_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "rdn_l1_bwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "rdn_ssim_workspace_size":(_i64, [_i32, _i32, _i32, _i32]),
     "rdn_ssim_fwd": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "rdn_ssim_bwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp]),
     "rdn_sqnorm": (_i32, [_vp, _i64, _f32, _vp, _vp, _vp]),

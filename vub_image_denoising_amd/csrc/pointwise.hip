@@ -356,6 +356,56 @@ __global__ void charb_bwd_kernel(const float* __restrict__ p, const float* __res
   }
 }
 
+// L1 (nn.L1Loss, mean): the same two levels.  n4 16-byte units go through 128-bit loads
+// (0 when a pointer is not 16-byte aligned), the rest element by element; every thread's
+// addition order is fixed by (n, n4, grid), so the sum does not depend on timing.
+__global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict__ p, const float* __restrict__ t,
+                                                         int64_t n, int64_t n4, float* __restrict__ part) {
+  float s = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const f32x4 a = ((const f32x4*)p)[i], b = ((const f32x4*)t)[i];
+    s += (fabsf(a[0] - b[0]) + fabsf(a[1] - b[1])) + (fabsf(a[2] - b[2]) + fabsf(a[3] - b[3]));
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    s += fabsf(p[i] - t[i]);
+  __shared__ float sh[4];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+__global__ __launch_bounds__(256) void l1_final_kernel(const float* __restrict__ part, int nb, int64_t n,
+                                                       float* __restrict__ out) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nb; i += 256) s += part[i];
+  __shared__ double sh[256];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)(sh[0] / (double)n);
+}
+
+// torch.sign: -1, 0, +1 (0 for a tie, -0.0 against 0.0 included, and for NaN)
+__device__ __forceinline__ float l1_sgn(float d) { return (float)((d > 0.f) - (d < 0.f)); }
+
+__global__ __launch_bounds__(256) void l1_bwd_kernel(const float* __restrict__ p, const float* __restrict__ t, int64_t n,
+                                                     int64_t n4, const float* __restrict__ gout, float* __restrict__ dp) {
+  const float g = gout[0] / (float)n;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const f32x4 a = ((const f32x4*)p)[i], b = ((const f32x4*)t)[i];
+    f32x4 o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = g * l1_sgn(a[q] - b[q]);
+    ((f32x4*)dp)[i] = o;
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    dp[i] = g * l1_sgn(p[i] - t[i]);
+}
+
 __global__ __launch_bounds__(256) void sq_partial_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ part) {
   float s = 0.f;
   const int64_t n4 = n / 4;
@@ -672,6 +722,28 @@ extern "C" int rdn_charbonnier_bwd(const float* pred, const float* target, int64
   if (!pred || !target || !gout || !dpred || count <= 0) { rdn_set_error("rdn_charbonnier_bwd: bad arguments"); return RDN_E_ARG; }
   charb_bwd_kernel<<<grid_for(count, 256 * 4), 256, 0, RDN_STREAM>>>(pred, target, count, eps * eps, wc, wm, gout, dpred);
   return rdn_check_launch("rdn_charbonnier_bwd");
+}
+
+// 16-byte units the L1 kernels may take through 128-bit accesses: all of count / 4 when
+// every pointer is 16-byte aligned, none otherwise (a view at an odd element offset)
+static int64_t l1_vec_units(int64_t count, const void* a, const void* b, const void* c) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) ? 0 : count / 4;
+}
+
+extern "C" int rdn_l1_fwd(const float* pred, const float* target, int64_t count, float* ws, float* out, void* stream) {
+  if (!pred || !target || !ws || !out || count <= 0) { rdn_set_error("rdn_l1_fwd: bad arguments"); return RDN_E_ARG; }
+  const int nb = grid_for(count, 256 * 8, kRedBlocks);
+  l1_partial_kernel<<<nb, 256, 0, RDN_STREAM>>>(pred, target, count, l1_vec_units(count, pred, target, nullptr), ws);
+  l1_final_kernel<<<1, 256, 0, RDN_STREAM>>>(ws, nb, count, out);
+  return rdn_check_launch("rdn_l1_fwd");
+}
+
+extern "C" int rdn_l1_bwd(const float* pred, const float* target, int64_t count, const float* gout, float* dpred,
+                          void* stream) {
+  if (!pred || !target || !gout || !dpred || count <= 0) { rdn_set_error("rdn_l1_bwd: bad arguments"); return RDN_E_ARG; }
+  l1_bwd_kernel<<<grid_for(count, 256 * 8, 2048), 256, 0, RDN_STREAM>>>(pred, target, count,
+                                                                        l1_vec_units(count, pred, target, dpred), gout, dpred);
+  return rdn_check_launch("rdn_l1_bwd");
 }
 
 extern "C" int rdn_sqnorm_scaled(const float* g, int64_t count, float max_norm, float pre_scale, float* ws, float* out,

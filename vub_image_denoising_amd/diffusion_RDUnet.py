@@ -276,15 +276,20 @@ def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, ou
                 writer.flush()
         if scheduler is not None:
             scheduler.step()
-        checkpoint_path = os.path.join(output_dir, f"diffusion_RDUNet_model_checkpointed_epoch_{epoch + 1}.pth")
-        os.makedirs(os.path.dirname(checkpoint_path) or ".", exist_ok=True)
-        torch.save({
-            'epoch': epoch + 1,
-            'model_state_dict': model.state_dict(),
-            'optimizer_state_dict': optimizer.state_dict(),
-            'scheduler_state_dict': scheduler.state_dict() if scheduler is not None else None,
-        }, checkpoint_path)
-        print(f"Model checkpoint saved at {checkpoint_path}")
+        save_epoch_checkpoint(model, optimizer, scheduler, epoch + 1, os.path.join(
+            output_dir, f"diffusion_RDUNet_model_checkpointed_epoch_{epoch + 1}.pth"))
+
+
+def save_epoch_checkpoint(model, optimizer, scheduler, epoch, checkpoint_path):
+    """The per-epoch checkpoint dict of the trainers (:166-174; ``epoch`` counts from 1)."""
+    os.makedirs(os.path.dirname(checkpoint_path) or ".", exist_ok=True)
+    torch.save({
+        'epoch': epoch,
+        'model_state_dict': model.state_dict(),
+        'optimizer_state_dict': optimizer.state_dict(),
+        'scheduler_state_dict': scheduler.state_dict() if scheduler is not None else None,
+    }, checkpoint_path)
+    print(f"Model checkpoint saved at {checkpoint_path}")
 
 
 def load_checkpoint(model, optimizer, scheduler, checkpoint_path):

@@ -6,6 +6,8 @@
   forward reduction (Charbonnier and MSE in one pass) and fused backward
 * ``ssim_fused``       — the SSIM term of ``combined_loss`` (pytorch_msssim.ssim,
   diffusion_RDUnet.py:60-65): ``rdn_ssim_fwd`` forward, ``rdn_ssim_bwd`` backward
+* ``l1_loss``          — ``nn.L1Loss`` of the plain RDUNet baseline's trainer
+  (UNet/RDUNet_model.py:201-215): ``rdn_l1_fwd`` forward, ``rdn_l1_bwd`` backward
 * ``clip_grad_norm_``  — torch.nn.utils.clip_grad_norm_ (diffusion_RDUnet.py:113)
   on the flat gradient buffer: one norm reduction + one scale, coefficient kept
   on the device
@@ -112,6 +114,42 @@ class _SsimFused(torch.autograd.Function):
         dx = torch.empty_like(x)
         _ssim_grad(H.lib(), x, y, coef, 1.0, _f32c(g.reshape(1)), dx, False)
         return dx, None, None
+
+
+class _L1Loss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target):
+        pred, target = _f32c(pred), _f32c(target)
+        if pred.shape != target.shape:
+            raise RuntimeError(f"l1_loss: shapes differ, {tuple(pred.shape)} and {tuple(target.shape)}")
+        n = pred.numel()
+        lib = H.lib()
+        ws = torch.empty(max(lib.rdn_reduce_workspace_size(n) // 4, 1), dtype=torch.float32, device=pred.device)
+        out = torch.empty(1, dtype=torch.float32, device=pred.device)
+        H.check(lib.rdn_l1_fwd(pred.data_ptr(), target.data_ptr(), n, ws.data_ptr(), out.data_ptr(), H.stream_ptr()),
+                "l1_fwd")
+        ctx.save_for_backward(pred, target)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target = ctx.saved_tensors
+        g = _f32c(g.reshape(1))
+        dp = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
+        H.check(H.lib().rdn_l1_bwd(pred.data_ptr(), target.data_ptr(), pred.numel(), g.data_ptr(), dp.data_ptr(),
+                                   H.stream_ptr()), "l1_bwd")
+        dt = -dp if ctx.needs_input_grad[1] else None
+        return dp, dt
+
+
+def l1_loss(pred, target):
+    """``nn.L1Loss()(pred, target)``, mean|pred - target| (the plain RDUNet baseline's
+    loss, UNet/RDUNet_model.py:201-215), as two launches: ``rdn_l1_fwd`` forward (a 0-dim
+    device tensor, no host sync, the same bits for the same input) and ``rdn_l1_bwd``
+    backward, ``sign(pred - target) * g / n`` with ``sign(0) = 0`` as aten's; the
+    target's gradient is its negative."""
+    H.require_device(pred, target)
+    return _L1Loss.apply(pred, target)
 
 
 def charbonnier_loss(pred, target, epsilon=1e-3):

@@ -35,6 +35,11 @@ The accumulator is one flat fp32 buffer of the gradient layout per model
 its own flat buffer and ONE flat ``add_`` folds it in (eager accumulation is 207
 per-tensor adds of the same elements: the same bits).  After an accumulate replay the
 parameters' ``.grad`` are views of the accumulator, as after eager accumulation.
+
+The model may also be a bare ``RDUNet`` (the plain baseline, RDUNet_model.train_model):
+the network is then the model itself and the body is the baseline's batch -- no t draw,
+no interpolation, ``L1(model(noisy), clean)`` -- in the same four kinds.  Such a graph
+has no t buffer (passing ``t`` raises) and no loss weights.
 """
 from __future__ import annotations
 
@@ -42,6 +47,7 @@ import os
 
 import torch
 
+from . import RDUNet_model as baseline
 from .diffusion_RDUnet import forward_step_device, sample_biased, train_step_device
 from .engine import find_flat
 from .functional import clip_grad_norm_, loss_weights_or_default
@@ -53,6 +59,12 @@ _FUSED_SURFACE = ("graph_buffers", "graph_key", "use_device_step", "set_step", "
 def is_fused(optimizer) -> bool:
     """The optimizer has what a captured step needs (optim.FusedFlatOptimizer's surface)."""
     return all(hasattr(optimizer, a) for a in _FUSED_SURFACE)
+
+
+def network_of(model):
+    """The fused network a step trains: a DiffusionModel's ``unet``, or the model itself
+    (a bare RDUNet, the baseline)."""
+    return getattr(model, "unet", model)
 
 
 def grad_accumulator(fp):
@@ -71,7 +83,7 @@ def grad_accumulator(fp):
 def clear_accumulator(model):
     """Discard a partial accumulation group (the trainers' ``optimizer.zero_grad()`` at the
     start of an epoch)."""
-    fp = getattr(model.unet, "_rdn_flat", None)
+    fp = getattr(network_of(model), "_rdn_flat", None)
     if fp is not None and getattr(fp, "_accum", None) is not None:
         fp._accum.zero_()
 
@@ -132,7 +144,11 @@ class TrainStepGraph:
             raise TypeError("TrainStepGraph needs a fused optimizer (optim.FusedAdam / FusedAdamW / FusedAdadelta)")
         if kind not in KINDS:
             raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
-        sync = getattr(getattr(model.unet, "_rdn_flat", None), "grad_sync", None)
+        self.net = network_of(model)
+        self.baseline = self.net is model     # no t, no interpolation, L1 loss (RDUNet_model.train_step_device)
+        if self.baseline and (t_input or loss_weights is not None):
+            raise ValueError("a bare RDUNet's step has no t input and no loss weights (its loss is L1)")
+        sync = getattr(getattr(self.net, "_rdn_flat", None), "grad_sync", None)
         if kind != 'step' and sync is not None and sync.world > 1:
             raise NotImplementedError(f"data-parallel capture of kind {kind!r} is not implemented (only 'step')")
         self.kind = kind
@@ -143,7 +159,7 @@ class TrainStepGraph:
         self.dev = dev
         self.clean = torch.zeros(shape, dtype=torch.float32, device=dev)
         self.noisy = torch.zeros(shape, dtype=torch.float32, device=dev)
-        self.host_t = distribution_choice == 'biased'
+        self.host_t = distribution_choice == 'biased' and not self.baseline
         self.t = torch.zeros(shape[0], dtype=torch.float32, device=dev) if (t_input or self.host_t) else None
         self.graph = None
         self._build(warmup)
@@ -154,24 +170,33 @@ class TrainStepGraph:
         weights, the compute dtype, and the addresses of the buffers the optimizer
         updates (a rebound optimizer or a re-flattened model re-captures instead of
         replaying onto freed memory)."""
-        return (self.opt.graph_key(), float(self.clip), self.model.unet.compute_dtype,
-                loss_weights_or_default(self.loss_weights))
+        return (self.opt.graph_key(), float(self.clip), self.net.compute_dtype,
+                'l1' if self.baseline else loss_weights_or_default(self.loss_weights))
+
+    def _train_step(self, clip=True):
+        """Backward of this batch alone (gradients zeroed first), clipped or not."""
+        if self.baseline:
+            return baseline.train_step_device(self.model, self.noisy, self.clean, self.opt, self.clip,
+                                              zero_grad=True, clip=clip)
+        return train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t,
+                                 clip=clip, loss_weights=self.loss_weights)
 
     def _body(self):
         if self.kind == 'loss':
+            if self.baseline:
+                self.model.train()
+                return baseline.forward_loss_device(self.model, self.noisy, self.clean)
             return forward_step_device(self.model, self.clean, self.noisy, self.dist, t=self.t, need_loss=True,
                                        loss_weights=self.loss_weights)
         if self.kind == 'step':
-            loss = train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t,
-                                     loss_weights=self.loss_weights)
+            loss = self._train_step()
             self.opt.step()
             return loss
         # 'accum' / 'accum_step': this backward's gradient lands in a flat buffer of its
         # own (the parameters' .grad are dropped first), one flat add folds it into the
         # accumulator, and .grad become the accumulator's views, which clip and the
         # update then see as the flat gradient
-        loss = train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t,
-                                 clip=False, loss_weights=self.loss_weights)
+        loss = self._train_step(clip=False)
         params = list(self.model.parameters())
         fp = find_flat(params)
         if fp is None:
@@ -194,8 +219,7 @@ class TrainStepGraph:
         with torch.cuda.stream(side):
             if find_flat(params) is None or self.opt._fp is None:
                 # gradients as flat views, so the optimizer can bind (no update yet)
-                train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t,
-                                  loss_weights=self.loss_weights)
+                self._train_step()
             self.opt.use_device_step()
             fp, opt = self.opt._fp, self.opt
             state = [fp.flat] + opt.graph_buffers()
@@ -212,7 +236,7 @@ class TrainStepGraph:
         torch.cuda.synchronize(self.dev)
         _drain_collectives(fp)
         fp.generation += 1
-        for wp in self.model.unet._rdn_packs.values():
+        for wp in self.net._rdn_packs.values():
             wp.key = None          # the weight repack is the graph's first launch
         self.graph = None
         g = torch.cuda.CUDAGraph(keep_graph=True)
@@ -242,7 +266,8 @@ class TrainStepGraph:
                 t = sample_biased(self.clean.size(0), self.model.timesteps)
             self.t.copy_(t)
         elif t is not None:
-            raise ValueError("this graph draws t itself (build it with t_input=True to pass t)")
+            raise ValueError("a bare RDUNet's step takes no t" if self.baseline else
+                             "this graph draws t itself (build it with t_input=True to pass t)")
         self.graph.replay()
         if self.kind in ('step', 'accum_step'):
             self.opt._replayed()
@@ -282,7 +307,12 @@ def trainer_graphs(model, optimizer, distribution_choice='uniform', clip_value=1
     if not is_fused(optimizer):
         raise TypeError("captured training needs a fused optimizer: build it with make_optimizer(..., fused=True) "
                         f"(optim.FusedAdam / FusedAdamW / FusedAdadelta), got {type(optimizer).__name__}")
-    key = (distribution_choice, float(clip_value), loss_weights_or_default(loss_weights))
+    if network_of(model) is model:   # a bare RDUNet: no t distribution, L1 loss
+        if loss_weights is not None:
+            raise ValueError("a bare RDUNet trains on L1: no loss weights")
+        key = ('l1', float(clip_value))
+    else:
+        key = (distribution_choice, float(clip_value), loss_weights_or_default(loss_weights))
     table = model.__dict__.setdefault("_rdn_train_graphs", {})
     g = table.get(key)
     if g is None or g.opt is not optimizer:

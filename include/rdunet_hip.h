@@ -35,6 +35,10 @@
  *   rdn_sqnorm / rdn_clip_scale  torch.nn.utils.clip_grad_norm_, diffusion_RDUnet.py:113.
  *   rdn_adam_step     torch.optim.Adam / AdamW step, diffusion_RDUnet.py:264-268,127.
  *   rdn_adadelta_step torch.optim.Adadelta step, diffusion_RDUnet.py:270-272,127.
+ *   rdn_ema_update    exponential moving average of the weights (no reference counterpart:
+ *                     the reference samples from the raw last-step weights).
+ *   rdn_adam_step_ema / rdn_adadelta_step_ema  the optimizer steps above with the average
+ *                     updated in the same launch (no reference counterpart).
  *   rdn_sampling_combine  the x_t update of improved_sampling, diffusion_RDUnet.py:45-49.
  *   rdn_synth_batch   CustomDataset/CustomSIDD_Dataset.__getitem__ + transforms
  *                     (dataset_creation/custom_dataset.py:64-100, SIDD_dataset.py:74-97).
@@ -372,6 +376,28 @@ int rdn_adam_step(float* p, const float* g, float* m, float* v, int64_t count,
    pointer or count < 0 returns RDN_E_ARG before any launch. */
 int rdn_adadelta_step(float* p, const float* g, float* square_avg, float* acc_delta, int64_t count,
                       double lr, double rho, double eps, double weight_decay, float grad_scale, void* stream);
+/* Exponential moving average of the weights over flat fp32 buffers (no reference
+   counterpart):  e = fmaf(w, p - e, e),  w = (float)(1 - d), uncontracted otherwise.
+   warmup == 0: d = decay.  warmup != 0: d = min(decay, (1 + n) / (10 + n)), n the number
+   of updates already done (the first update has n = 0, d = 0.1); with n_dev != NULL n is
+   read from device memory instead and w derived on the device from the same double
+   expression (a graph-replayable update).  No launch here writes *n_dev: advance it with
+   rdn_counter_inc behind the update.  16 bytes per lane where both buffers are 16-byte
+   aligned, scalar otherwise.  Where p = e = 0 (the padding gaps of a flat parameter buffer)
+   e stays 0.  count == 0 is a no-op; a null ema or p, count < 0, a decay outside [0, 1] or
+   a host n < 0 returns RDN_E_ARG before any launch. */
+int rdn_ema_update(float* ema, const float* p, int64_t count, double decay, int32_t warmup, int64_t n,
+                   const int64_t* n_dev, void* stream);
+/* rdn_adam_step / rdn_adadelta_step with the average of the just-computed p updated in
+   the same launch (the same kernel bodies; p and the moments get the plain entries'
+   bits, ema the bits of rdn_ema_update run behind them).  ema has the layout of p. */
+int rdn_adam_step_ema(float* p, const float* g, float* m, float* v, int64_t count,
+                      double lr, double beta1, double beta2, double eps, double wd, int32_t decoupled,
+                      int64_t step, const int64_t* step_dev, float grad_scale,
+                      float* ema, double decay, int32_t warmup, int64_t n, const int64_t* n_dev, void* stream);
+int rdn_adadelta_step_ema(float* p, const float* g, float* square_avg, float* acc_delta, int64_t count,
+                          double lr, double rho, double eps, double weight_decay, float grad_scale,
+                          float* ema, double decay, int32_t warmup, int64_t n, const int64_t* n_dev, void* stream);
 /* *counter += 1 on the device (one thread; stream-ordered) */
 int rdn_counter_inc(int64_t* counter, void* stream);
 /* buf[slot] = the device wall clock (constant rate, rdn_wall_clock_khz ticks per ms) when

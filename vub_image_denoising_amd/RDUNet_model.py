@@ -86,10 +86,11 @@ def forward_loss_device(model, noisy, clean):
 
 CHECKPOINT_NAME = "RDUNet_model_epoch_{epoch}.pth"
 FINAL_NAME = "RDUNet_model_final.pth"
+FINAL_EMA_NAME = "RDUNet_model_final_ema.pth"
 
 
 def train_model(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir, num_epochs,
-                start_epoch=0, accumulation_steps=4, clip_value=1.0, log_every=1, captured=False):
+                start_epoch=0, accumulation_steps=4, clip_value=1.0, log_every=1, captured=False, ema=None):
     """RDUNet_model.py:201-261: every epoch starts with ``zero_grad`` (a partial
     accumulation group left by the previous epoch is dropped), each batch adds its L1
     gradient, every ``accumulation_steps``-th batch clips, steps and zeroes; then one
@@ -100,12 +101,15 @@ def train_model(model, train_loader, val_loader, optimizer, scheduler, writer, o
     ``captured=True`` replays each batch as one hipGraph (the ``'accum'`` and
     ``'accum_step'`` kinds of ``train_graph``, kept on the model) and needs a fused
     optimizer (``optim.FusedAdamW``): parameters, optimizer state and logged losses are
-    the eager loop's bit for bit."""
-    from .diffusion_RDUnet import save_epoch_checkpoint
+    the eager loop's bit for bit.  ``ema`` (optim.EMA): an average of the weights kept with
+    every update, as in diffusion_RDUnet.run_epochs -- ``Loss/validation_ema`` is the same
+    validation batch under the averaged weights, the checkpoints gain ``ema_state_dict``."""
+    from .diffusion_RDUnet import save_epoch_checkpoint, use_ema
     graphs = None
     if captured:
         from . import train_graph
         graphs = train_graph.trainer_graphs(model, optimizer, clip_value=clip_value)
+    ema_update = use_ema(model, optimizer, ema)
     dev = next(model.parameters()).device
     for epoch in range(start_epoch, num_epochs):
         model.train()
@@ -121,7 +125,11 @@ def train_model(model, train_loader, val_loader, optimizer, scheduler, writer, o
             else:
                 loss_t = train_step_device(model, noisy, clean, optimizer, clip_value, clip=step_now)
                 if step_now:
+                    if ema_update:
+                        ema.bind()      # (first step: the average starts as the weights before it)
                     optimizer.step()
+                    if ema_update:
+                        ema.update()
                     optimizer.zero_grad()
             if batch_idx % log_every == 0:
                 loss = loss_t.item()
@@ -129,31 +137,43 @@ def train_model(model, train_loader, val_loader, optimizer, scheduler, writer, o
                 if writer is not None:
                     writer.add_scalar('Loss/train', loss, epoch * n_batches + batch_idx)
         model.eval()
-        validation_loss = float("nan")
+        validation_loss = ema_loss = float("nan")
         if val_loader is not None:
             val_noisy, val_clean = next(iter(val_loader))
-            validation_loss = forward_loss_device(model, val_noisy.to(dev), val_clean.to(dev)).item()
+            val_noisy, val_clean = val_noisy.to(dev), val_clean.to(dev)
+            validation_loss = forward_loss_device(model, val_noisy, val_clean).item()
+            if ema is not None:
+                with ema.applied():
+                    ema_loss = forward_loss_device(model, val_noisy, val_clean).item()
         print(f"Epoch [{epoch + 1}/{num_epochs}], Validation Loss: {validation_loss:.4f}")
+        if ema is not None:
+            print(f"Epoch [{epoch + 1}/{num_epochs}], Validation Loss (EMA weights): {ema_loss:.4f}")
         if writer is not None:
             writer.add_scalar('Loss/validation', validation_loss, epoch + 1)
+            if ema is not None:
+                writer.add_scalar('Loss/validation_ema', ema_loss, epoch + 1)
             if hasattr(writer, "flush"):
                 writer.flush()
         if scheduler is not None:
             scheduler.step()
         save_epoch_checkpoint(model, optimizer, scheduler, epoch + 1,
-                              os.path.join(output_dir, CHECKPOINT_NAME.format(epoch=epoch + 1)))
+                              os.path.join(output_dir, CHECKPOINT_NAME.format(epoch=epoch + 1)), ema=ema)
 
 
-def load_checkpoint(model, optimizer, scheduler, checkpoint_path):
+def load_checkpoint(model, optimizer, scheduler, checkpoint_path, *, ema=None):
     """Resume from a per-epoch checkpoint dict of ``train_model`` (returns its epoch), or
     load the bare ``state_dict`` that ``train`` writes at the end (weights only: the
-    optimizer and scheduler stay as built, returns 0)."""
+    optimizer and scheduler stay as built, returns 0).  ``ema`` (optim.EMA) is restored
+    from the checkpoint's ``ema_state_dict``, or restarted from the loaded weights where
+    there is none (diffusion_RDUnet.restore_ema)."""
+    from .diffusion_RDUnet import restore_ema
     if (checkpoint_path is not None) and os.path.isfile(checkpoint_path):
         print(f"Loading checkpoint '{checkpoint_path}'")
         dev = next(model.parameters()).device
         checkpoint = torch.load(checkpoint_path, map_location=dev, weights_only=True)
         if 'model_state_dict' not in checkpoint:
             model.load_state_dict(checkpoint)
+            restore_ema(ema, None, model)
             print(f"Loaded weights '{checkpoint_path}'")
             return 0
         model.load_state_dict(checkpoint['model_state_dict'])
@@ -161,6 +181,7 @@ def load_checkpoint(model, optimizer, scheduler, checkpoint_path):
             optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
         if scheduler is not None and checkpoint.get('scheduler_state_dict') is not None:
             scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
+        restore_ema(ema, checkpoint, model)
         start_epoch = checkpoint['epoch']
         print(f"Loaded checkpoint '{checkpoint_path}' (epoch {start_epoch})")
         return start_epoch
@@ -182,7 +203,7 @@ def make_optimizer(args, params, fused=False):
 def train(args, train_loader=None, val_loader=None):
     """Build ``RDUNet(base_filters=args.base_filters)``, AdamW and StepLR, resume from
     ``args.checkpoint_path`` and run ``train_model`` (TensorBoard if importable)."""
-    from .diffusion_RDUnet import load_data
+    from .diffusion_RDUnet import load_data, make_ema, save_final_ema
     try:
         from torch.utils.tensorboard import SummaryWriter
         writer = SummaryWriter(log_dir=os.path.join("runs", "RDUNet", os.path.basename(args.output_dir)))
@@ -196,13 +217,16 @@ def train(args, train_loader=None, val_loader=None):
     model.apply(init_weights())
     captured = args.step_mode == 'graph'
     optimizer, scheduler = make_optimizer(args, model.parameters(), fused=captured)
-    start_epoch = load_checkpoint(model, optimizer, scheduler, args.checkpoint_path)
+    ema = make_ema(args, model)
+    start_epoch = load_checkpoint(model, optimizer, scheduler, args.checkpoint_path, ema=ema)
     train_model(model, train_loader, val_loader, optimizer, scheduler, writer, args.output_dir, args.num_epochs,
-                start_epoch=start_epoch, accumulation_steps=args.accumulation_steps, captured=captured)
+                start_epoch=start_epoch, accumulation_steps=args.accumulation_steps, captured=captured, ema=ema)
     final_model_path = os.path.join(args.output_dir, FINAL_NAME)
     os.makedirs(args.output_dir, exist_ok=True)
     torch.save(model.state_dict(), final_model_path)
     print(f"Final model saved at {final_model_path}")
+    if ema is not None:
+        save_final_ema(model, ema, os.path.join(args.output_dir, FINAL_EMA_NAME))
     if writer is not None:
         writer.close()
 
@@ -230,6 +254,8 @@ def build_parser():
                         help="graph: fused AdamW, every batch replayed as one captured hipGraph")
     parser.add_argument('--data_pipeline', type=str, default='pil', choices=['pil', 'gpu'],
                         help="gpu: patches cut and augmented on the device (synth loaders), no worker processes")
+    from .diffusion_RDUnet import add_ema_arguments
+    add_ema_arguments(parser)
     return parser
 
 

@@ -135,6 +135,11 @@ SIGNATURES = {
                              _i32, _i64, _vp, _f32, _vp]),
     "rdn_adadelta_step": (_i32, [_vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _f32,
                                  _vp]),
+    "rdn_ema_update": (_i32, [_vp, _vp, _i64, C.c_double, _i32, _i64, _vp, _vp]),
+    "rdn_adam_step_ema": (_i32, [_vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                 _i32, _i64, _vp, _f32, _vp, C.c_double, _i32, _i64, _vp, _vp]),
+    "rdn_adadelta_step_ema": (_i32, [_vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _f32,
+                                     _vp, C.c_double, _i32, _i64, _vp, _vp]),
     "rdn_counter_inc": (_i32, [_vp, _vp]),
     "rdn_stamp": (_i32, [_vp, _i32, _vp]),
     "rdn_wall_clock_khz": (_i64, []),

@@ -476,12 +476,51 @@ __host__ __device__ inline AdamScalars adam_scalars(double lr, double b1, double
   return a;
 }
 
+// Exponential moving average of the weights (no reference counterpart): one element is
+//   e = fmaf(w, p - e, e),  w = (float)(1 - d)
+// with d = decay, or with warm-up d = min(decay, (1 + n) / (10 + n)) for the update after
+// n earlier ones.  w is rounded once from double, on the host for a host-known n and on
+// the device, from the same double expression, when n is read from device memory (a
+// replayed graph).  In the flat layout's padding gaps p = e = 0, so e stays 0.
+__host__ __device__ inline float ema_weight(double decay, int warmup, int64_t n) {
+  double d = decay;
+  if (warmup) {
+    const double r = (1.0 + (double)n) / (10.0 + (double)n);
+    d = r < d ? r : d;
+  }
+  return (float)(1.0 - d);
+}
+
+__device__ __forceinline__ void ema_elem(float& e, float p, float w) {
+#pragma clang fp contract(off)
+  e = fmaf(w, p - e, e);
+}
+
+// what an update kernel needs to keep the average: host_w is the weight of a host-known
+// count; with n_dev != nullptr (warm-up in a replayable step) the count is read from
+// device memory by thread 0 of every block -- nothing in the launch writes it (the
+// counter is advanced by rdn_counter_inc behind the launch, stream-ordered)
+struct EmaArgs {
+  float* e;
+  float host_w;
+  double decay;
+  const int64_t* n_dev;
+};
+
+__device__ __forceinline__ float ema_block_weight(const EmaArgs& a) {
+  __shared__ float w_s;
+  if (!a.n_dev) return a.host_w;
+  if (threadIdx.x == 0) w_s = ema_weight(a.decay, 1, *a.n_dev);
+  __syncthreads();
+  return w_s;
+}
+
 // host_sc: the scalars of a host-known step; with step_dev != nullptr the step count
 // is read from device memory (graph-replayable optimizer step) and the scalars are
 // derived on the device in double, exactly as on the host
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, int64_t n, AdamScalars host_sc, const int64_t* __restrict__ step_dev,
-                            double lr, double b1, double b2, double eps, double wd, int decoupled, float gs) {
+__device__ __forceinline__ AdamScalars adam_block_scalars(const AdamScalars& host_sc,
+                                                          const int64_t* __restrict__ step_dev, double lr, double b1,
+                                                          double b2, double eps, double wd, int decoupled) {
   __shared__ AdamScalars sc_s;
   AdamScalars sc = host_sc;
   if (step_dev) {
@@ -489,7 +528,17 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     __syncthreads();
     sc = sc_s;
   }
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+  return sc;
+}
+
+// EMA: the average of the just-computed p is updated in the same pass (e in the layout of
+// p, weight ew).  tid / stride: the grid-stride geometry, read in the __global__ functions
+// themselves (read in an inlined body, blockDim compiles to the slower generic load).
+template <bool EMA>
+__device__ __forceinline__ void adam_loop(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, int64_t n, const AdamScalars& sc, float gs,
+                                          float* __restrict__ e, float ew, int64_t tid, int64_t stride) {
+  for (int64_t i = tid; i < n; i += stride) {
     float pi = p[i], gi = g[i] * gs;
     pi *= sc.decay;
     gi += sc.wd * pi;
@@ -499,7 +548,30 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     v[i] = vi;
     pi += -sc.step_size * (mi / (sqrtf(vi) / sc.bc2s + sc.eps));
     p[i] = pi;
+    if constexpr (EMA) {
+      float ei = e[i];
+      ema_elem(ei, pi, ew);
+      e[i] = ei;
+    }
   }
+}
+
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                            float* __restrict__ v, int64_t n, AdamScalars host_sc, const int64_t* __restrict__ step_dev,
+                            double lr, double b1, double b2, double eps, double wd, int decoupled, float gs) {
+  const AdamScalars sc = adam_block_scalars(host_sc, step_dev, lr, b1, b2, eps, wd, decoupled);
+  adam_loop<false>(p, g, m, v, n, sc, gs, nullptr, 0.f, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                   (int64_t)gridDim.x * blockDim.x);
+}
+
+__global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                float* __restrict__ v, int64_t n, AdamScalars host_sc,
+                                const int64_t* __restrict__ step_dev, double lr, double b1, double b2, double eps,
+                                double wd, int decoupled, float gs, EmaArgs ema) {
+  const AdamScalars sc = adam_block_scalars(host_sc, step_dev, lr, b1, b2, eps, wd, decoupled);
+  const float ew = ema_block_weight(ema);
+  adam_loop<true>(p, g, m, v, n, sc, gs, ema.e, ew, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                  (int64_t)gridDim.x * blockDim.x);
 }
 
 // torch.optim.Adadelta single-tensor math (torch/optim/adadelta.py, _single_tensor_adadelta),
@@ -530,25 +602,72 @@ __device__ __forceinline__ void adadelta_elem(float& p, float g, float& sq, floa
   p = fmaf(sc.neg_lr, d, p);                      // add_(delta, alpha=-lr)
 }
 
-__global__ __launch_bounds__(256) void adadelta_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ sq, float* __restrict__ acc, int64_t n,
-                                                       int64_t n4, AdadeltaScalars sc, float gs) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (int64_t i = tid; i < n4; i += stride) {    // n4 = n/4 when all four buffers are 16-byte aligned, else 0
+template <bool EMA>
+__device__ __forceinline__ void adadelta_body(float* __restrict__ p, const float* __restrict__ g,
+                                              float* __restrict__ sq, float* __restrict__ acc, int64_t n, int64_t n4,
+                                              const AdadeltaScalars& sc, float gs, float* __restrict__ e, float ew,
+                                              int64_t tid, int64_t stride) {
+  for (int64_t i = tid; i < n4; i += stride) {    // n4 = n/4 when every buffer is 16-byte aligned, else 0
     f32x4 pv = ((f32x4*)p)[i], sv = ((f32x4*)sq)[i], av = ((f32x4*)acc)[i];
     const f32x4 gv = ((const f32x4*)g)[i];
+    f32x4 ev;
+    if constexpr (EMA) ev = ((f32x4*)e)[i];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float pk = pv[k], sk = sv[k], ak = av[k];
       adadelta_elem(pk, gv[k], sk, ak, sc, gs);
       pv[k] = pk; sv[k] = sk; av[k] = ak;
+      if constexpr (EMA) {
+        float ek = ev[k];
+        ema_elem(ek, pk, ew);
+        ev[k] = ek;
+      }
     }
     ((f32x4*)p)[i] = pv;
     ((f32x4*)sq)[i] = sv;
     ((f32x4*)acc)[i] = av;
+    if constexpr (EMA) ((f32x4*)e)[i] = ev;
   }
-  for (int64_t i = n4 * 4 + tid; i < n; i += stride) adadelta_elem(p[i], g[i], sq[i], acc[i], sc, gs);
+  for (int64_t i = n4 * 4 + tid; i < n; i += stride) {
+    adadelta_elem(p[i], g[i], sq[i], acc[i], sc, gs);
+    if constexpr (EMA) ema_elem(e[i], p[i], ew);
+  }
+}
+
+__global__ __launch_bounds__(256) void adadelta_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ sq, float* __restrict__ acc, int64_t n,
+                                                       int64_t n4, AdadeltaScalars sc, float gs) {
+  adadelta_body<false>(p, g, sq, acc, n, n4, sc, gs, nullptr, 0.f, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                       (int64_t)gridDim.x * blockDim.x);
+}
+
+__global__ __launch_bounds__(256) void adadelta_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ sq, float* __restrict__ acc, int64_t n,
+                                                           int64_t n4, AdadeltaScalars sc, float gs, EmaArgs ema) {
+  const float ew = ema_block_weight(ema);
+  adadelta_body<true>(p, g, sq, acc, n, n4, sc, gs, ema.e, ew, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                      (int64_t)gridDim.x * blockDim.x);
+}
+
+// the stand-alone average update (optimizers that are not fused): 16 bytes per lane
+// where both buffers are 16-byte aligned (n4 = n/4, else 0), scalar tail
+__global__ __launch_bounds__(256) void ema_kernel(const float* __restrict__ p, int64_t n, int64_t n4, EmaArgs ema) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const float ew = ema_block_weight(ema);
+  float* __restrict__ e = ema.e;
+  for (int64_t i = tid; i < n4; i += stride) {
+    const f32x4 pv = ((const f32x4*)p)[i];
+    f32x4 ev = ((f32x4*)e)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float ek = ev[k];
+      ema_elem(ek, pv[k], ew);
+      ev[k] = ek;
+    }
+    ((f32x4*)e)[i] = ev;
+  }
+  for (int64_t i = n4 * 4 + tid; i < n; i += stride) ema_elem(e[i], p[i], ew);
 }
 
 __global__ void counter_inc_kernel(int64_t* c) { *c += 1; }
@@ -768,11 +887,15 @@ extern "C" int rdn_clip_scale(float* g, int64_t count, const float* coef, void* 
   return rdn_check_launch("rdn_clip_scale");
 }
 
+static bool adam_args_ok(const float* p, const float* g, const float* m, const float* v, int64_t count, int64_t step,
+                         const int64_t* step_dev, double beta1, double beta2) {
+  return p && g && m && v && count > 0 && (step_dev || step >= 1) && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1;
+}
+
 extern "C" int rdn_adam_step(float* p, const float* g, float* m, float* v, int64_t count, double lr, double beta1,
                              double beta2, double eps, double wd, int32_t decoupled, int64_t step,
                              const int64_t* step_dev, float grad_scale, void* stream) {
-  if (!p || !g || !m || !v || count <= 0 || (!step_dev && step < 1) || beta1 < 0 || beta1 >= 1 || beta2 < 0 ||
-      beta2 >= 1) {
+  if (!adam_args_ok(p, g, m, v, count, step, step_dev, beta1, beta2)) {
     rdn_set_error("rdn_adam_step: bad arguments");
     return RDN_E_ARG;
   }
@@ -782,23 +905,88 @@ extern "C" int rdn_adam_step(float* p, const float* g, float* m, float* v, int64
   return rdn_check_launch("rdn_adam_step");
 }
 
-extern "C" int rdn_adadelta_step(float* p, const float* g, float* square_avg, float* acc_delta, int64_t count,
-                                 double lr, double rho, double eps, double weight_decay, float grad_scale,
-                                 void* stream) {
-  if (!p || !g || !square_avg || !acc_delta) { rdn_set_error("rdn_adadelta_step: null pointer"); return RDN_E_ARG; }
-  if (count < 0) { rdn_set_error("rdn_adadelta_step: count %lld < 0", (long long)count); return RDN_E_ARG; }
-  if (count == 0) return RDN_OK;
+// validates the average's arguments and fills the kernel's EmaArgs (false: RDN_E_ARG set)
+static bool ema_args(const char* who, float* ema, double decay, int32_t warmup, int64_t n, const int64_t* n_dev,
+                     EmaArgs* out) {
+  if (!ema) { rdn_set_error("%s: null ema buffer", who); return false; }
+  if (!(decay >= 0.0 && decay <= 1.0)) { rdn_set_error("%s: decay %g outside [0, 1]", who, decay); return false; }
+  if (n < 0 && !(warmup && n_dev)) { rdn_set_error("%s: update count %lld < 0", who, (long long)n); return false; }
+  out->e = ema;
+  out->host_w = ema_weight(decay, warmup != 0, n < 0 ? 0 : n);
+  out->decay = decay;
+  out->n_dev = warmup ? n_dev : nullptr;
+  return true;
+}
+
+extern "C" int rdn_adam_step_ema(float* p, const float* g, float* m, float* v, int64_t count, double lr, double beta1,
+                                 double beta2, double eps, double wd, int32_t decoupled, int64_t step,
+                                 const int64_t* step_dev, float grad_scale, float* ema, double decay, int32_t warmup,
+                                 int64_t n, const int64_t* n_dev, void* stream) {
+  if (!adam_args_ok(p, g, m, v, count, step, step_dev, beta1, beta2)) {
+    rdn_set_error("rdn_adam_step_ema: bad arguments");
+    return RDN_E_ARG;
+  }
+  EmaArgs ea;
+  if (!ema_args("rdn_adam_step_ema", ema, decay, warmup, n, n_dev, &ea)) return RDN_E_ARG;
+  const AdamScalars sc = adam_scalars(lr, beta1, beta2, eps, wd, decoupled, (double)(step < 1 ? 1 : step));
+  adam_ema_kernel<<<grid_for(count, 256 * 4), 256, 0, RDN_STREAM>>>(p, g, m, v, count, sc, step_dev, lr, beta1, beta2,
+                                                                   eps, wd, decoupled, grad_scale, ea);
+  return rdn_check_launch("rdn_adam_step_ema");
+}
+
+static AdadeltaScalars adadelta_scalars(double lr, double rho, double eps, double weight_decay) {
   AdadeltaScalars sc;
   sc.rho = (float)rho;
   sc.omr = (float)(1.0 - rho);
   sc.eps = (float)eps;
   sc.neg_lr = (float)(-lr);
   sc.wd = (float)weight_decay;
+  return sc;
+}
+
+extern "C" int rdn_adadelta_step(float* p, const float* g, float* square_avg, float* acc_delta, int64_t count,
+                                 double lr, double rho, double eps, double weight_decay, float grad_scale,
+                                 void* stream) {
+  if (!p || !g || !square_avg || !acc_delta) { rdn_set_error("rdn_adadelta_step: null pointer"); return RDN_E_ARG; }
+  if (count < 0) { rdn_set_error("rdn_adadelta_step: count %lld < 0", (long long)count); return RDN_E_ARG; }
+  if (count == 0) return RDN_OK;
+  const AdadeltaScalars sc = adadelta_scalars(lr, rho, eps, weight_decay);
   const bool aligned = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)square_avg | (uintptr_t)acc_delta) & 15) == 0;
   const int64_t n4 = aligned ? count / 4 : 0;
   adadelta_kernel<<<grid_for(aligned ? n4 + 3 : count, 256 * 4), 256, 0, RDN_STREAM>>>(p, g, square_avg, acc_delta, count,
                                                                                      n4, sc, grad_scale);
   return rdn_check_launch("rdn_adadelta_step");
+}
+
+extern "C" int rdn_adadelta_step_ema(float* p, const float* g, float* square_avg, float* acc_delta, int64_t count,
+                                     double lr, double rho, double eps, double weight_decay, float grad_scale,
+                                     float* ema, double decay, int32_t warmup, int64_t n, const int64_t* n_dev,
+                                     void* stream) {
+  if (!p || !g || !square_avg || !acc_delta) { rdn_set_error("rdn_adadelta_step_ema: null pointer"); return RDN_E_ARG; }
+  if (count < 0) { rdn_set_error("rdn_adadelta_step_ema: count %lld < 0", (long long)count); return RDN_E_ARG; }
+  EmaArgs ea;
+  if (!ema_args("rdn_adadelta_step_ema", ema, decay, warmup, n, n_dev, &ea)) return RDN_E_ARG;
+  if (count == 0) return RDN_OK;
+  const AdadeltaScalars sc = adadelta_scalars(lr, rho, eps, weight_decay);
+  const bool aligned = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)square_avg | (uintptr_t)acc_delta | (uintptr_t)ema) &
+                        15) == 0;
+  const int64_t n4 = aligned ? count / 4 : 0;
+  adadelta_ema_kernel<<<grid_for(aligned ? n4 + 3 : count, 256 * 4), 256, 0, RDN_STREAM>>>(
+      p, g, square_avg, acc_delta, count, n4, sc, grad_scale, ea);
+  return rdn_check_launch("rdn_adadelta_step_ema");
+}
+
+extern "C" int rdn_ema_update(float* ema, const float* p, int64_t count, double decay, int32_t warmup, int64_t n,
+                              const int64_t* n_dev, void* stream) {
+  if (!p) { rdn_set_error("rdn_ema_update: null parameter buffer"); return RDN_E_ARG; }
+  if (count < 0) { rdn_set_error("rdn_ema_update: count %lld < 0", (long long)count); return RDN_E_ARG; }
+  EmaArgs ea;
+  if (!ema_args("rdn_ema_update", ema, decay, warmup, n, n_dev, &ea)) return RDN_E_ARG;
+  if (count == 0) return RDN_OK;
+  const bool aligned = (((uintptr_t)ema | (uintptr_t)p) & 15) == 0;
+  const int64_t n4 = aligned ? count / 4 : 0;
+  ema_kernel<<<grid_for(aligned ? n4 + 3 : count, 256 * 4), 256, 0, RDN_STREAM>>>(p, count, n4, ea);
+  return rdn_check_launch("rdn_ema_update");
 }
 
 extern "C" int rdn_counter_inc(int64_t* counter, void* stream) {

@@ -8,6 +8,9 @@ through one captured sampler, blended back.  Pixels are normalised as in the loa
 (``(x/255 - 0.5)/0.5``) and written back with ``denormalize``, clamp and round.  The
 checkpoint is either form the trainers write -- the per-epoch dict with
 ``model_state_dict`` or the final bare ``state_dict`` -- read with ``weights_only=True``.
+``--weights ema`` takes the averaged weights of a per-epoch checkpoint trained with
+``--ema_decay`` (its ``ema_state_dict``); the ``*_final_ema.pth`` file is a bare
+``state_dict`` and loads as it is.
 """
 from __future__ import annotations
 
@@ -29,6 +32,8 @@ def build_parser():
     p.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
     p.add_argument('--base_filters', type=int, default=32)
     p.add_argument('--timesteps', type=int, default=20)
+    p.add_argument('--weights', type=str, default='model', choices=['model', 'ema'],
+                   help="ema: the averaged weights of a checkpoint trained with --ema_decay")
     return p
 
 
@@ -46,14 +51,18 @@ def tensor_to_image(t: torch.Tensor):
     return Image.fromarray(a.permute(1, 2, 0).contiguous().numpy())   # uint8 HWC: mode RGB
 
 
-def load_model(checkpoint, base_filters=32, timesteps=20, dtype="fp32", device="cuda"):
-    from .diffusion_RDUnet import DiffusionModel
+def load_model(checkpoint, base_filters=32, timesteps=20, dtype="fp32", device="cuda", weights="model"):
+    from .diffusion_RDUnet import DiffusionModel, ema_weights
     from .Unet_model import RDUNet_T
+    if weights not in ("model", "ema"):
+        raise ValueError(f"weights must be 'model' or 'ema', got {weights!r}")
     unet = RDUNet_T(base_filters=base_filters)
     unet.set_compute_dtype(dtype)
     model = DiffusionModel(unet, timesteps=timesteps)
     ckpt = torch.load(checkpoint, map_location="cpu", weights_only=True)
-    if isinstance(ckpt, dict) and "model_state_dict" in ckpt:
+    if weights == "ema":
+        ckpt = ema_weights(ckpt, checkpoint)
+    elif isinstance(ckpt, dict) and "model_state_dict" in ckpt:
         ckpt = ckpt["model_state_dict"]
     model.load_state_dict(ckpt)
     return model.to(device).eval()
@@ -64,7 +73,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("denoise_image runs on the ROCm GPU only (HIP kernels); no device found")
-    model = load_model(args.checkpoint, args.base_filters, args.timesteps, args.dtype)
+    model = load_model(args.checkpoint, args.base_filters, args.timesteps, args.dtype, weights=args.weights)
     with Image.open(args.input) as img:
         noisy = image_to_tensor(img).cuda()
     out = model.denoise_image(noisy, tile=args.tile, overlap=args.overlap, sampler=args.sampler)

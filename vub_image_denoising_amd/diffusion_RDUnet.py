@@ -169,26 +169,42 @@ def train_step_checkpointed(model, clean_images, noisy_images, optimizer, accumu
 def train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir,
                              distribution_choice='uniform', num_epochs=10, start_epoch=0, accumulation_steps=4,
                              clip_value=1.0, log_every=1, accumulation='reference', loss_weights=None, *,
-                             captured=False):
+                             captured=False, ema=None):
     """diffusion_RDUnet.py:117-178: epochs of train steps with the reference's
     every-``accumulation_steps`` optimizer step, one-batch improved_sampling
     validation, scheduler step and a checkpoint dict per epoch.  ``log_every``
     > 1 rate-limits the per-batch ``loss.item()`` host sync; ``accumulation``
     selects the reference's update rule or the fixed one (see run_epochs);
     ``loss_weights`` the loss mix of the train steps and the validation loss;
-    ``captured`` replays every batch as one hipGraph (fused optimizers only)."""
+    ``captured`` replays every batch as one hipGraph (fused optimizers only);
+    ``ema`` (optim.EMA) averages the weights after every update (see run_epochs)."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir, distribution_choice,
                num_epochs, start_epoch, accumulation_steps, clip_value, log_every,
                sample=lambda m, x: m.improved_sampling(x), accumulation=accumulation, loss_weights=loss_weights,
-               captured=captured)
+               captured=captured, ema=ema)
 
 
 ACCUMULATION_MODES = ("reference", "fixed")
 
 
+def use_ema(model, optimizer, ema):
+    """How a trainer keeps ``ema`` (optim.EMA, or None): a fused optimizer takes it into
+    its own launch (``attach_ema``: nothing more to do, eager or captured) and False is
+    returned; beside a torch optimizer the trainer calls ``ema.bind()`` before and
+    ``ema.update()`` after every ``optimizer.step()`` and True is returned.  The names of
+    ``ema.state_dict()['shadow']`` become those of ``model.state_dict()``."""
+    if ema is None:
+        return False
+    ema.use_names_of(model)
+    if hasattr(optimizer, "attach_ema"):
+        optimizer.attach_ema(ema)
+        return False
+    return True
+
+
 def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir, distribution_choice,
                num_epochs, start_epoch, accumulation_steps, clip_value, log_every, sample, accumulation='reference',
-               skip_discarded=True, loss_weights=None, captured=False):
+               skip_discarded=True, loss_weights=None, captured=False, ema=None):
     """The epoch loop shared by the three reference trainers (diffusion_RDUnet.py:117-178,
     main_diffusion_RDUnet.py:275-336, diffusion_RDUnet_direct.py:266-327); they
     differ only in the validation sampler and the checkpoint directory.
@@ -215,13 +231,20 @@ def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, ou
     a flat accumulator, the ``accumulation_steps``-th with clip and update.  The update
     is inside the graph, so the optimizer must be a fused one
     (``make_optimizer(..., fused=True)``); the parameters, optimizer state and logged
-    losses are the eager loop's bit for bit (``skip_discarded`` has no captured form)."""
+    losses are the eager loop's bit for bit (``skip_discarded`` has no captured form).
+
+    ``ema`` (optim.EMA, no reference counterpart): an exponential moving average of the
+    weights, updated with every optimizer update -- inside a fused optimizer's launch
+    (eager or captured), by ``ema.update()`` behind a torch optimizer's step.
+    ``Loss/validation`` stays the raw weights' loss; ``Loss/validation_ema`` logs the same
+    batch sampled with the averaged weights, and the checkpoints gain ``ema_state_dict``."""
     if accumulation not in ACCUMULATION_MODES:
         raise ValueError(f"accumulation must be one of {ACCUMULATION_MODES}, got {accumulation!r}")
     graphs = None
     if captured:
         from . import train_graph
         graphs = train_graph.trainer_graphs(model, optimizer, distribution_choice, clip_value, loss_weights)
+    ema_update = use_ema(model, optimizer, ema)
     dev = next(model.parameters()).device
     for epoch in range(start_epoch, num_epochs):
         model.train()
@@ -253,7 +276,11 @@ def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, ou
                 loss_t = forward_step_device(model, clean_images, noisy_images, distribution_choice,
                                              need_loss=log_now, loss_weights=loss_weights)
             if step_now and not captured:
+                if ema_update:
+                    ema.bind()      # (first step: the average starts as the weights before it)
                 optimizer.step()
+                if ema_update:
+                    ema.update()
                 optimizer.zero_grad()
             if log_now:
                 loss = loss_t.item()
@@ -261,7 +288,7 @@ def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, ou
                 if writer is not None:
                     writer.add_scalar('Loss/train', loss, epoch * n_batches + batch_idx)
         model.eval()
-        validation_loss = float("nan")
+        validation_loss = ema_loss = float("nan")
         if val_loader is not None:
             with torch.no_grad():
                 val_noisy_images, val_clean_images = next(iter(val_loader))
@@ -269,31 +296,69 @@ def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, ou
                 denoised_images = sample(model, val_noisy_images)
                 validation_loss = combined_loss(denoised_images, val_clean_images,
                                                 *Fn.loss_weights_or_default(loss_weights)).item()
+                if ema is not None:
+                    with ema.applied():
+                        ema_loss = combined_loss(sample(model, val_noisy_images), val_clean_images,
+                                                 *Fn.loss_weights_or_default(loss_weights)).item()
         print(f"Epoch [{epoch + 1}/{num_epochs}], Validation Loss: {validation_loss:.4f}")
+        if ema is not None:
+            print(f"Epoch [{epoch + 1}/{num_epochs}], Validation Loss (EMA weights): {ema_loss:.4f}")
         if writer is not None:
             writer.add_scalar('Loss/validation', validation_loss, epoch + 1)
+            if ema is not None:
+                writer.add_scalar('Loss/validation_ema', ema_loss, epoch + 1)
             if hasattr(writer, "flush"):
                 writer.flush()
         if scheduler is not None:
             scheduler.step()
         save_epoch_checkpoint(model, optimizer, scheduler, epoch + 1, os.path.join(
-            output_dir, f"diffusion_RDUNet_model_checkpointed_epoch_{epoch + 1}.pth"))
+            output_dir, f"diffusion_RDUNet_model_checkpointed_epoch_{epoch + 1}.pth"), ema=ema)
 
 
-def save_epoch_checkpoint(model, optimizer, scheduler, epoch, checkpoint_path):
-    """The per-epoch checkpoint dict of the trainers (:166-174; ``epoch`` counts from 1)."""
+def save_epoch_checkpoint(model, optimizer, scheduler, epoch, checkpoint_path, ema=None):
+    """The per-epoch checkpoint dict of the trainers (:166-174; ``epoch`` counts from 1);
+    with an EMA also ``ema_state_dict`` (optim.EMA.state_dict(); no reference counterpart)."""
     os.makedirs(os.path.dirname(checkpoint_path) or ".", exist_ok=True)
-    torch.save({
+    checkpoint = {
         'epoch': epoch,
         'model_state_dict': model.state_dict(),
         'optimizer_state_dict': optimizer.state_dict(),
         'scheduler_state_dict': scheduler.state_dict() if scheduler is not None else None,
-    }, checkpoint_path)
+    }
+    if ema is not None:
+        ema.use_names_of(model)
+        checkpoint['ema_state_dict'] = ema.state_dict()
+    torch.save(checkpoint, checkpoint_path)
     print(f"Model checkpoint saved at {checkpoint_path}")
 
 
-def load_checkpoint(model, optimizer, scheduler, checkpoint_path):
-    """diffusion_RDUnet.py:180-193 (weights-only safe load)."""
+def restore_ema(ema, checkpoint, model):
+    """The EMA part of a ``load_checkpoint`` (after the weights are loaded): restore it from
+    ``ema_state_dict``; a checkpoint without one restarts the average from the loaded
+    weights at count 0."""
+    if ema is None:
+        return
+    ema.use_names_of(model)
+    if isinstance(checkpoint, dict) and checkpoint.get('ema_state_dict') is not None:
+        ema.load_state_dict(checkpoint['ema_state_dict'])
+    else:
+        ema.reset_to_weights()
+        print("Checkpoint has no EMA: the average restarts from the loaded weights (0 updates)")
+
+
+def ema_weights(checkpoint, checkpoint_path=""):
+    """The averaged weights of a per-epoch checkpoint dict (``ema_state_dict['shadow']``);
+    a clear error when it was trained without an EMA."""
+    state = checkpoint.get('ema_state_dict') if isinstance(checkpoint, dict) else None
+    if state is None:
+        raise KeyError(f"checkpoint {checkpoint_path!r} holds no EMA weights (no 'ema_state_dict': it was trained "
+                       "without --ema_decay, or it is a bare state_dict; the file train() writes as "
+                       "*_final_ema.pth loads with weights='model')")
+    return state['shadow']
+
+
+def load_checkpoint(model, optimizer, scheduler, checkpoint_path, *, ema=None):
+    """diffusion_RDUnet.py:180-193 (weights-only safe load); ``ema``: restored too (restore_ema)."""
     if (checkpoint_path is not None) and os.path.isfile(checkpoint_path):
         print(f"Loading checkpoint '{checkpoint_path}'")
         dev = next(model.parameters()).device
@@ -302,6 +367,7 @@ def load_checkpoint(model, optimizer, scheduler, checkpoint_path):
         optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
         if scheduler is not None and checkpoint.get('scheduler_state_dict') is not None:
             scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
+        restore_ema(ema, checkpoint, model)
         start_epoch = checkpoint['epoch']
         print(f"Loaded checkpoint '{checkpoint_path}' (epoch {start_epoch})")
         return start_epoch
@@ -350,6 +416,38 @@ def make_optimizer(args, params, fused=False):
     return optimizer, scheduler
 
 
+def add_ema_arguments(parser):
+    """``--ema_decay`` / ``--ema_warmup`` (no reference counterpart), on every trainer's parser.
+    Optional additions to the reference's namespaces: a flag that is not given leaves no
+    attribute behind (``argparse.SUPPRESS``) and ``make_ema`` reads them with the defaults
+    0 (no EMA) and False."""
+    parser.add_argument('--ema_decay', type=float, default=argparse.SUPPRESS,
+                        help="keep an exponential moving average of the weights with this decay (default 0: none), "
+                             "validate with it too and save it in the checkpoints")
+    parser.add_argument('--ema_warmup', action='store_true', default=argparse.SUPPRESS,
+                        help="ramp the EMA decay as min(decay, (1 + n) / (10 + n)) over the first updates")
+    return parser
+
+
+def make_ema(args, model):
+    """The optim.EMA the ``--ema_decay`` / ``--ema_warmup`` flags ask for, or None."""
+    decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
+    if decay <= 0.0:
+        return None
+    from .optim import EMA
+    return EMA(model, decay, warmup=bool(getattr(args, "ema_warmup", False)))
+
+
+def save_final_ema(model, ema, path):
+    """The averaged weights as a bare ``state_dict`` of ``model`` (what ``denoise_image
+    --checkpoint`` and ``model.load_state_dict`` take as it is)."""
+    ema.use_names_of(model)
+    state = model.state_dict()
+    state.update(ema.state_dict()['shadow'])
+    torch.save(state, path)
+    print(f"Final EMA weights saved at {path}")
+
+
 def train(args, train_loader=None, val_loader=None):
     """diffusion_RDUnet.py:230-288 (TensorBoard if importable)."""
     try:
@@ -365,22 +463,25 @@ def train(args, train_loader=None, val_loader=None):
     unet.apply(init_weights())
     captured = getattr(args, "step_mode", "eager") == 'graph'
     optimizer, scheduler = make_optimizer(args, model.parameters(), fused=captured)
-    start_epoch = load_checkpoint(model, optimizer, scheduler, args.checkpoint_path)
+    ema = make_ema(args, model)
+    start_epoch = load_checkpoint(model, optimizer, scheduler, args.checkpoint_path, ema=ema)
     train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, args.output_dir,
                              args.distribution_choice, num_epochs=args.num_epochs, start_epoch=start_epoch,
                              accumulation=getattr(args, "accumulation", "reference"),
                              loss_weights=(getattr(args, "mse_weight", 0.0), getattr(args, "charbonnier_weight", 1.0),
-                                           getattr(args, "ssim_weight", 0.0)), captured=captured)
+                                           getattr(args, "ssim_weight", 0.0)), captured=captured, ema=ema)
     final_model_path = os.path.join(args.output_dir, "diffusion_RDUNet_model_checkpointed_final.pth")
     torch.save(model.state_dict(), final_model_path)
     print(f"Final model saved at {final_model_path}")
+    if ema is not None:
+        save_final_ema(model, ema, os.path.join(args.output_dir, "diffusion_RDUNet_model_checkpointed_final_ema.pth"))
     if writer is not None:
         writer.close()
 
 
 def build_parser():
     """diffusion_RDUnet.py:293-309, plus --dtype, --accumulation, the three
-    weights of ``combined_loss`` (:60), --step_mode and --data_pipeline."""
+    weights of ``combined_loss`` (:60), --step_mode, --data_pipeline and the EMA flags."""
     parser = argparse.ArgumentParser(description="Train a diffusion model with optional optimizer and scheduler choice.")
     parser.add_argument('--dataset_choice', type=str, default='SIDD', choices=['DIV2K', 'SIDD'])
     parser.add_argument('--checkpoint_path', type=str, default=None)
@@ -409,6 +510,7 @@ def build_parser():
                         help="graph: fused optimizer, every batch replayed as one captured hipGraph")
     parser.add_argument('--data_pipeline', type=str, default='pil', choices=['pil', 'gpu'],
                         help="gpu: patches cut and augmented on the device (synth loaders), no worker processes")
+    add_ema_arguments(parser)
     return parser
 
 

@@ -10,7 +10,8 @@ from . import diffusion_RDUnet as _base
 from .diffusion_RDUnet import (charbonnier_loss, combined_loss, denormalize, device, run_epochs,  # noqa: F401
                                train_step_device)
 from . import main_diffusion_RDUnet as _main
-from .main_diffusion_RDUnet import CHECKPOINT_DIR, load_checkpoint, train_step_checkpointed  # noqa: F401
+from .main_diffusion_RDUnet import (CHECKPOINT_DIR, build_parser, load_checkpoint, make_ema,  # noqa: F401
+                                    train_step_checkpointed)
 from .Unet_model import (DenoisingBlock, DownsampleBlock, InputBlock, OutputBlock, RDUNet_T,  # noqa: F401
                          UpsampleBlock, init_weights)
 
@@ -34,8 +35,9 @@ def _sample(model, x):
 
 def train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, num_epochs=10,
                              start_epoch=0, accumulation_steps=4, clip_value=1.0, *, accumulation='reference',
-                             loss_weights=None, captured=False):
-    """diffusion_RDUnet_direct.py:266-327 (validation with direct_sampling; ``captured``: see run_epochs)."""
+                             loss_weights=None, captured=False, ema=None):
+    """diffusion_RDUnet_direct.py:266-327 (validation with direct_sampling; ``captured``, ``ema``: see
+    run_epochs)."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, CHECKPOINT_DIR, 'uniform', num_epochs,
                start_epoch, accumulation_steps, clip_value, 1, sample=_sample, accumulation=accumulation,
-               loss_weights=loss_weights, captured=captured)
+               loss_weights=loss_weights, captured=captured, ema=ema)

@@ -256,16 +256,18 @@ SIDE_BATCH = max(1, min(8, int(os.environ.get("RDN_SIDE_BATCH", "4"))))
 FWD_CHUNK_PIXELS = 1 << 23
 
 
-def find_flat(params):
+def find_flat(params, need_grads=True):
     """The FlatParams whose parameter list is exactly ``params`` (same objects,
     same order) with every gradient its view of one flat gradient buffer
-    (which becomes its ``gflat``), else None."""
+    (which becomes its ``gflat``), else None.  ``need_grads=False`` drops the gradient
+    condition (what only reads or writes the weights: optim.EMA)."""
     params = list(params)
     for ref in _FLAT_REGISTRY:
         fp = ref()
         if fp is None or len(fp.params) != len(params):
             continue
-        if all(a is b for a, b in zip(fp.params, params)) and fp.intact() and fp.grads_are_views():
+        if (all(a is b for a, b in zip(fp.params, params)) and fp.intact()
+                and (not need_grads or fp.grads_are_views())):
             return fp
     return None
 

@@ -23,8 +23,8 @@ import torch
 import torch.optim as optim
 from torch.optim.lr_scheduler import CosineAnnealingLR
 
-from .diffusion_RDUnet import (DiffusionModel, charbonnier_loss, combined_loss, denormalize, device,  # noqa: F401
-                               run_epochs, train_step_device)
+from .diffusion_RDUnet import (DiffusionModel, add_ema_arguments, charbonnier_loss, combined_loss,  # noqa: F401
+                               denormalize, device, make_ema, restore_ema, run_epochs, train_step_device)
 from .Unet_model import (DenoisingBlock, DownsampleBlock, InputBlock, OutputBlock, RDUNet_T,  # noqa: F401
                          UpsampleBlock, init_weights)
 
@@ -47,6 +47,14 @@ def make_training_objects(base_filters=32, lr=2e-4, dev=None, model_cls=None, fu
     return unet, model, optimizer, scheduler
 
 
+def build_parser():
+    """The reference script takes no flags (its settings are module-level constants); the
+    only ones here are this package's own: ``--ema_decay`` / ``--ema_warmup``, which
+    ``make_ema(args, model)`` turns into the ``ema`` of ``train_model_checkpointed``."""
+    import argparse
+    return add_ema_arguments(argparse.ArgumentParser(description="EMA options of the main_diffusion_RDUnet trainer."))
+
+
 def train_step_checkpointed(model, clean_images, noisy_images, optimizer, accumulation_steps, clip_value=0.1, *,
                             loss_weights=None):
     """main_diffusion_RDUnet.py:237-273 (uniform t; returns ``loss.item()``)."""
@@ -60,15 +68,16 @@ def _sample(model, x):
 
 def train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, num_epochs=10,
                              start_epoch=0, accumulation_steps=4, clip_value=1.0, *, accumulation='reference',
-                             loss_weights=None, captured=False):
-    """main_diffusion_RDUnet.py:275-336 (``captured``: see run_epochs)."""
+                             loss_weights=None, captured=False, ema=None):
+    """main_diffusion_RDUnet.py:275-336 (``captured``, ``ema``: see run_epochs)."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, CHECKPOINT_DIR, 'uniform', num_epochs,
                start_epoch, accumulation_steps, clip_value, 1, sample=_sample, accumulation=accumulation,
-               loss_weights=loss_weights, captured=captured)
+               loss_weights=loss_weights, captured=captured, ema=ema)
 
 
-def load_checkpoint(model, optimizer, scheduler, checkpoint_path):
-    """main_diffusion_RDUnet.py:339-352 (weights-only safe load)."""
+def load_checkpoint(model, optimizer, scheduler, checkpoint_path, *, ema=None):
+    """main_diffusion_RDUnet.py:339-352 (weights-only safe load); ``ema``: restored too
+    (diffusion_RDUnet.restore_ema)."""
     if os.path.isfile(checkpoint_path):
         print(f"Loading checkpoint '{checkpoint_path}'")
         dev = next(model.parameters()).device
@@ -76,6 +85,7 @@ def load_checkpoint(model, optimizer, scheduler, checkpoint_path):
         model.load_state_dict(checkpoint['model_state_dict'])
         optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
         scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
+        restore_ema(ema, checkpoint, model)
         start_epoch = checkpoint['epoch']
         print(f"Loaded checkpoint '{checkpoint_path}' (epoch {start_epoch})")
         return start_epoch

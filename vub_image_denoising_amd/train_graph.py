@@ -13,6 +13,11 @@ What makes the step capturable:
   next step;
 * the Adam step count lives in device memory (FusedAdam.use_device_step), so
   bias corrections advance on every replay;
+* an EMA attached to the optimizer (optim.EMA, FusedFlatOptimizer.attach_ema) is
+  updated by the optimizer's own launch: its shadow buffer and, with warm-up, its
+  device update counter are part of ``graph_buffers()`` (rolled back over the warm-up
+  steps like the moments) and of ``graph_key()``; only ``step`` / ``accum_step``
+  replays touch it;
 * ``torch.randint`` t draws use torch's graph-safe Philox generator (every
   replay advances its offset exactly as an eager step does); the 'biased'
   distribution draws on the CPU in the reference (:71-73), so its t are drawn
@@ -227,11 +232,15 @@ class TrainStepGraph:
                 state.append(grad_accumulator(fp)[0])   # may hold a partial group: kept
             snap = [b.clone() for b in state]
             step0 = opt._step
+            ema = getattr(opt, "ema", None)
+            ema0 = 0 if ema is None else ema.num_updates
             for _ in range(max(1, warmup)):
                 self._body()
             for b, s in zip(state, snap):
                 b.copy_(s)
             opt.set_step(step0)
+            if ema is not None:
+                ema.num_updates = ema0       # (its device counter is one of the restored buffers)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize(self.dev)
         _drain_collectives(fp)
@@ -248,6 +257,8 @@ class TrainStepGraph:
         self._captured = self._hyper()
         # capture ran nothing: undo its host-side effects (step count, pack keys)
         opt.set_step(step0, device=False)
+        if ema is not None:
+            ema.num_updates = ema0
         fp.generation += 1
         torch.cuda.set_rng_state(rng, self.dev)
 
@@ -255,6 +266,10 @@ class TrainStepGraph:
     def __call__(self, clean_images, noisy_images, t=None):
         """One train step on this batch; returns the loss (a device tensor, valid
         until the next call)."""
+        ema = getattr(self.opt, "ema", None)
+        if ema is not None and ema.swapped:
+            raise RuntimeError("TrainStepGraph: the optimizer's EMA is swapped into the weights (inside "
+                               "EMA.applied()); swap back before training on")
         if self._hyper() != self._captured:
             self._build(1)
         self.clean.copy_(clean_images)

@@ -33,7 +33,10 @@ import sys
 import torch
 
 from . import functional as Fn
+from . import trainer
 from .engine import run_unet
+from .trainer import (add_data_arguments, add_ema_arguments, load_data, make_ema, restore_ema,  # noqa: F401
+                      save_epoch_checkpoint, save_final_ema, train_epochs, use_ema)
 from .Unet_model import (DenoisingBlock, DownsampleBlock, InputBlock, OutputBlock,  # noqa: F401
                          UpsampleBlock, _RDUNetBase, init_weights)
 
@@ -49,6 +52,13 @@ class RDUNet(_RDUNetBase):
 
     def forward(self, inputs):
         return run_unet(self, inputs, None)
+
+    def train_task(self, distribution_choice='uniform', loss_weights=None):
+        """What a train batch of this model is, for ``trainer`` and ``train_graph``: L1, no t
+        (``distribution_choice`` has nothing to choose)."""
+        if loss_weights is not None:
+            raise ValueError("a bare RDUNet trains on L1: no loss weights")
+        return L1Task(self)
 
 
 def denormalize(tensor):
@@ -89,104 +99,46 @@ FINAL_NAME = "RDUNet_model_final.pth"
 FINAL_EMA_NAME = "RDUNet_model_final_ema.pth"
 
 
+class L1Task:
+    """What a batch of the baseline's trainer is (see ``trainer``): ``L1(model(noisy), clean)``,
+    no t; the steps are this module's ``train_step_device`` / ``forward_loss_device``."""
+    takes_t = host_t = False
+    graph_key = ('l1',)
+
+    def __init__(self, model):
+        self.model = self.network = model
+
+    def train_batch(self, clean, noisy, optimizer, clip_value, zero_grad=True, clip=True, t=None):
+        return train_step_device(self.model, noisy, clean, optimizer, clip_value, zero_grad=zero_grad, clip=clip)
+
+    def loss_batch(self, clean, noisy, need_loss=True, t=None):
+        self.model.train()
+        return forward_loss_device(self.model, noisy, clean)
+
+    def validation_loss(self, clean, noisy):
+        return forward_loss_device(self.model, noisy, clean)
+
+
 def train_model(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir, num_epochs,
                 start_epoch=0, accumulation_steps=4, clip_value=1.0, log_every=1, captured=False, ema=None):
-    """RDUNet_model.py:201-261: every epoch starts with ``zero_grad`` (a partial
-    accumulation group left by the previous epoch is dropped), each batch adds its L1
-    gradient, every ``accumulation_steps``-th batch clips, steps and zeroes; then one
-    validation batch (``Loss/validation``), ``scheduler.step()`` and a checkpoint dict
-    (``epoch``, ``model_state_dict``, ``optimizer_state_dict``, ``scheduler_state_dict``;
-    the parameter names are the network's own, without a ``unet.`` prefix).
-    ``log_every`` > 1 rate-limits the per-batch ``loss.item()`` host sync.
-    ``captured=True`` replays each batch as one hipGraph (the ``'accum'`` and
-    ``'accum_step'`` kinds of ``train_graph``, kept on the model) and needs a fused
-    optimizer (``optim.FusedAdamW``): parameters, optimizer state and logged losses are
-    the eager loop's bit for bit.  ``ema`` (optim.EMA): an average of the weights kept with
-    every update, as in diffusion_RDUnet.run_epochs -- ``Loss/validation_ema`` is the same
-    validation batch under the averaged weights, the checkpoints gain ``ema_state_dict``."""
-    from .diffusion_RDUnet import save_epoch_checkpoint, use_ema
-    graphs = None
-    if captured:
-        from . import train_graph
-        graphs = train_graph.trainer_graphs(model, optimizer, clip_value=clip_value)
-    ema_update = use_ema(model, optimizer, ema)
-    dev = next(model.parameters()).device
-    for epoch in range(start_epoch, num_epochs):
-        model.train()
-        optimizer.zero_grad()
-        if captured:
-            train_graph.clear_accumulator(model)
-        n_batches = len(train_loader) if hasattr(train_loader, "__len__") else 0
-        for batch_idx, (noisy, clean) in enumerate(train_loader):
-            noisy, clean = noisy.to(dev), clean.to(dev)
-            step_now = (batch_idx + 1) % accumulation_steps == 0
-            if captured:
-                loss_t = graphs(clean, noisy, kind='accum_step' if step_now else 'accum')
-            else:
-                loss_t = train_step_device(model, noisy, clean, optimizer, clip_value, clip=step_now)
-                if step_now:
-                    if ema_update:
-                        ema.bind()      # (first step: the average starts as the weights before it)
-                    optimizer.step()
-                    if ema_update:
-                        ema.update()
-                    optimizer.zero_grad()
-            if batch_idx % log_every == 0:
-                loss = loss_t.item()
-                print(f"Epoch [{epoch + 1}/{num_epochs}], Batch [{batch_idx + 1}/{n_batches}], Loss: {loss:.4f}")
-                if writer is not None:
-                    writer.add_scalar('Loss/train', loss, epoch * n_batches + batch_idx)
-        model.eval()
-        validation_loss = ema_loss = float("nan")
-        if val_loader is not None:
-            val_noisy, val_clean = next(iter(val_loader))
-            val_noisy, val_clean = val_noisy.to(dev), val_clean.to(dev)
-            validation_loss = forward_loss_device(model, val_noisy, val_clean).item()
-            if ema is not None:
-                with ema.applied():
-                    ema_loss = forward_loss_device(model, val_noisy, val_clean).item()
-        print(f"Epoch [{epoch + 1}/{num_epochs}], Validation Loss: {validation_loss:.4f}")
-        if ema is not None:
-            print(f"Epoch [{epoch + 1}/{num_epochs}], Validation Loss (EMA weights): {ema_loss:.4f}")
-        if writer is not None:
-            writer.add_scalar('Loss/validation', validation_loss, epoch + 1)
-            if ema is not None:
-                writer.add_scalar('Loss/validation_ema', ema_loss, epoch + 1)
-            if hasattr(writer, "flush"):
-                writer.flush()
-        if scheduler is not None:
-            scheduler.step()
-        save_epoch_checkpoint(model, optimizer, scheduler, epoch + 1,
-                              os.path.join(output_dir, CHECKPOINT_NAME.format(epoch=epoch + 1)), ema=ema)
+    """RDUNet_model.py:201-261: ``trainer.train_epochs`` on an ``L1Task`` with the fixed
+    accumulation rule (see there for ``log_every``, ``captured`` and ``ema``) -- each batch adds
+    its L1 gradient, every ``accumulation_steps``-th batch clips, steps and zeroes.  The
+    checkpoint dicts' parameter names are the network's own, without a ``unet.`` prefix; a
+    captured run replays the ``'accum'`` / ``'accum_step'`` kinds of ``train_graph`` and needs
+    ``optim.FusedAdamW``."""
+    train_epochs(L1Task(model), train_loader, val_loader, optimizer, scheduler, writer,
+                 os.path.join(output_dir, CHECKPOINT_NAME), num_epochs, start_epoch, accumulation_steps, clip_value,
+                 log_every, accumulation='fixed', captured=captured, ema=ema)
 
 
 def load_checkpoint(model, optimizer, scheduler, checkpoint_path, *, ema=None):
     """Resume from a per-epoch checkpoint dict of ``train_model`` (returns its epoch), or
     load the bare ``state_dict`` that ``train`` writes at the end (weights only: the
-    optimizer and scheduler stay as built, returns 0).  ``ema`` (optim.EMA) is restored
-    from the checkpoint's ``ema_state_dict``, or restarted from the loaded weights where
-    there is none (diffusion_RDUnet.restore_ema)."""
-    from .diffusion_RDUnet import restore_ema
-    if (checkpoint_path is not None) and os.path.isfile(checkpoint_path):
-        print(f"Loading checkpoint '{checkpoint_path}'")
-        dev = next(model.parameters()).device
-        checkpoint = torch.load(checkpoint_path, map_location=dev, weights_only=True)
-        if 'model_state_dict' not in checkpoint:
-            model.load_state_dict(checkpoint)
-            restore_ema(ema, None, model)
-            print(f"Loaded weights '{checkpoint_path}'")
-            return 0
-        model.load_state_dict(checkpoint['model_state_dict'])
-        if optimizer is not None:
-            optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
-        if scheduler is not None and checkpoint.get('scheduler_state_dict') is not None:
-            scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
-        restore_ema(ema, checkpoint, model)
-        start_epoch = checkpoint['epoch']
-        print(f"Loaded checkpoint '{checkpoint_path}' (epoch {start_epoch})")
-        return start_epoch
-    print(f"No checkpoint found at '{checkpoint_path}'")
-    return 0
+    optimizer and scheduler stay as built, returns 0); the optimizer may be None.  ``ema``
+    (optim.EMA) is restored from the checkpoint's ``ema_state_dict``, or restarted from the
+    loaded weights where there is none (trainer.restore_ema)."""
+    return trainer.load_checkpoint(model, optimizer, scheduler, checkpoint_path, ema=ema, bare_weights=True)
 
 
 def make_optimizer(args, params, fused=False):
@@ -203,7 +155,6 @@ def make_optimizer(args, params, fused=False):
 def train(args, train_loader=None, val_loader=None):
     """Build ``RDUNet(base_filters=args.base_filters)``, AdamW and StepLR, resume from
     ``args.checkpoint_path`` and run ``train_model`` (TensorBoard if importable)."""
-    from .diffusion_RDUnet import load_data, make_ema, save_final_ema
     try:
         from torch.utils.tensorboard import SummaryWriter
         writer = SummaryWriter(log_dir=os.path.join("runs", "RDUNet", os.path.basename(args.output_dir)))
@@ -236,25 +187,11 @@ def build_parser():
     reference's width of 128, AdamW's ``--lr`` / ``--weight_decay`` and the
     accumulation group size."""
     parser = argparse.ArgumentParser(description="Train the plain RDUNet baseline (L1 loss, AdamW, StepLR).")
-    parser.add_argument('--dataset_choice', type=str, default='SIDD', choices=['DIV2K', 'SIDD'])
-    parser.add_argument('--checkpoint_path', type=str, default=None)
-    parser.add_argument('--num_epochs', type=int, default=300)
-    parser.add_argument('--batch_size', type=int, default=8)
-    parser.add_argument('--num_workers', type=int, default=8)
-    parser.add_argument('--validation_split', type=float, default=0.2)
-    parser.add_argument('--augment', action='store_false')
-    parser.add_argument('--dataset_percentage', type=float, default=0.1)
+    add_data_arguments(parser)
     parser.add_argument('--base_filters', type=int, default=128)
-    parser.add_argument('--output_dir', type=str, default='checkpoints')
     parser.add_argument('--lr', type=float, default=1e-4)
     parser.add_argument('--weight_decay', type=float, default=1e-4)
     parser.add_argument('--accumulation_steps', type=int, default=4)
-    parser.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
-    parser.add_argument('--step_mode', type=str, default='eager', choices=['eager', 'graph'],
-                        help="graph: fused AdamW, every batch replayed as one captured hipGraph")
-    parser.add_argument('--data_pipeline', type=str, default='pil', choices=['pil', 'gpu'],
-                        help="gpu: patches cut and augmented on the device (synth loaders), no worker processes")
-    from .diffusion_RDUnet import add_ema_arguments
     add_ema_arguments(parser)
     return parser
 

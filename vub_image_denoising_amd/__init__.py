@@ -9,6 +9,8 @@ Drop-in modules (same names/signatures as the reference):
   diffusion_RDUnet  DiffusionModel, charbonnier_loss, combined_loss,
                     train_step_checkpointed, train_model_checkpointed, ...
   data_loader       load_data (DIV2K-style folder loader, synthetic loader)
+Shared by the trainers: trainer (the epoch loop, checkpoints, EMA plumbing, flags),
+train_graph (captured steps), optim (fused optimizers, EMA).
 Compute runs in librdunet_hip.so (hand-written HIP kernels, C ABI in
 include/rdunet_hip.h); see DESIGN.md.
 """

@@ -28,6 +28,9 @@ import torch.optim as optim
 from torch.optim.lr_scheduler import CosineAnnealingLR
 
 from . import functional as Fn
+from .trainer import (ACCUMULATION_MODES, add_data_arguments, add_ema_arguments, ema_weights,  # noqa: F401
+                      load_checkpoint, load_data, make_ema, restore_ema, save_epoch_checkpoint, save_final_ema,
+                      train_epochs, use_ema)
 from .Unet_model import RDUNet_T, init_weights  # noqa: F401
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -64,6 +67,10 @@ class DiffusionModel(nn.Module):
     def forward(self, clean_image, noisy_image, t):
         noisy_step_image = self.forward_diffusion(clean_image, noisy_image, t)
         return self.improved_sampling(noisy_step_image)
+
+    def train_task(self, distribution_choice='uniform', loss_weights=None):
+        """What a train batch of this model is, for ``trainer`` and ``train_graph``."""
+        return DiffusionTask(self, distribution_choice, loss_weights)
 
 
 charbonnier_loss = Fn.charbonnier_loss
@@ -103,7 +110,7 @@ def train_step_device(model, clean_images, noisy_images, optimizer, distribution
     """The body of train_step_checkpointed without the host sync: returns the
     loss as a device tensor.  ``t`` (integer steps, [B]) overrides the draw.
     ``zero_grad=False, clip=False`` accumulates into the existing gradients
-    (the fixed accumulation mode of run_epochs).  ``loss_weights``: the
+    (the fixed accumulation mode of trainer.train_epochs).  ``loss_weights``: the
     ``(mse, charbonnier, ssim)`` weights of ``combined_loss``, None for the
     reference's (0, 1, 0)."""
     model.train()
@@ -170,230 +177,69 @@ def train_model_checkpointed(model, train_loader, val_loader, optimizer, schedul
                              distribution_choice='uniform', num_epochs=10, start_epoch=0, accumulation_steps=4,
                              clip_value=1.0, log_every=1, accumulation='reference', loss_weights=None, *,
                              captured=False, ema=None):
-    """diffusion_RDUnet.py:117-178: epochs of train steps with the reference's
-    every-``accumulation_steps`` optimizer step, one-batch improved_sampling
-    validation, scheduler step and a checkpoint dict per epoch.  ``log_every``
-    > 1 rate-limits the per-batch ``loss.item()`` host sync; ``accumulation``
-    selects the reference's update rule or the fixed one (see run_epochs);
-    ``loss_weights`` the loss mix of the train steps and the validation loss;
-    ``captured`` replays every batch as one hipGraph (fused optimizers only);
-    ``ema`` (optim.EMA) averages the weights after every update (see run_epochs)."""
+    """diffusion_RDUnet.py:117-178: ``run_epochs`` with the one-batch improved_sampling
+    validation (``log_every``, ``accumulation``, ``captured`` and ``ema``: see
+    trainer.train_epochs; ``loss_weights``: the loss mix of the train steps and the validation)."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir, distribution_choice,
                num_epochs, start_epoch, accumulation_steps, clip_value, log_every,
                sample=lambda m, x: m.improved_sampling(x), accumulation=accumulation, loss_weights=loss_weights,
                captured=captured, ema=ema)
 
 
-ACCUMULATION_MODES = ("reference", "fixed")
+CHECKPOINT_NAME = "diffusion_RDUNet_model_checkpointed_epoch_{epoch}.pth"
 
 
-def use_ema(model, optimizer, ema):
-    """How a trainer keeps ``ema`` (optim.EMA, or None): a fused optimizer takes it into
-    its own launch (``attach_ema``: nothing more to do, eager or captured) and False is
-    returned; beside a torch optimizer the trainer calls ``ema.bind()`` before and
-    ``ema.update()`` after every ``optimizer.step()`` and True is returned.  The names of
-    ``ema.state_dict()['shadow']`` become those of ``model.state_dict()``."""
-    if ema is None:
-        return False
-    ema.use_names_of(model)
-    if hasattr(optimizer, "attach_ema"):
-        optimizer.attach_ema(ema)
-        return False
-    return True
+class DiffusionTask:
+    """What a batch of the diffusion trainers is (see ``trainer``): this module's
+    ``train_step_device`` / ``forward_step_device`` with ``distribution_choice`` and
+    ``loss_weights``; validation samples one batch with ``sample(model, noisy)``."""
+    takes_t = True
+
+    def __init__(self, model, distribution_choice='uniform', loss_weights=None, sample=None):
+        self.model, self.sample = model, sample
+        self.distribution_choice, self.loss_weights = distribution_choice, loss_weights
+        self.host_t = distribution_choice == 'biased'   # drawn on the CPU, as the reference does (:71-73)
+        self.graph_key = (distribution_choice, Fn.loss_weights_or_default(loss_weights))
+
+    @property
+    def network(self):
+        return self.model.unet
+
+    def draw_t(self, batch_size):
+        return sample_biased(batch_size, self.model.timesteps)
+
+    def train_batch(self, clean_images, noisy_images, optimizer, clip_value, zero_grad=True, clip=True, t=None):
+        # the step's own clip is for this backward's gradient alone (it folds the data-parallel
+        # average in); gradients accumulated over batches are clipped as a whole afterwards
+        loss = train_step_device(self.model, clean_images, noisy_images, optimizer, self.distribution_choice,
+                                 clip_value, t=t, zero_grad=zero_grad, clip=clip and zero_grad,
+                                 loss_weights=self.loss_weights)
+        if clip and not zero_grad:
+            Fn.clip_grad_norm_(self.model.parameters(), clip_value)
+        return loss
+
+    def loss_batch(self, clean_images, noisy_images, need_loss=True, t=None):
+        return forward_step_device(self.model, clean_images, noisy_images, self.distribution_choice, t=t,
+                                   need_loss=need_loss, loss_weights=self.loss_weights)
+
+    def validation_loss(self, clean_images, noisy_images):
+        with torch.no_grad():
+            return combined_loss(self.sample(self.model, noisy_images), clean_images,
+                                 *Fn.loss_weights_or_default(self.loss_weights))
 
 
 def run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, output_dir, distribution_choice,
                num_epochs, start_epoch, accumulation_steps, clip_value, log_every, sample, accumulation='reference',
                skip_discarded=True, loss_weights=None, captured=False, ema=None):
     """The epoch loop shared by the three reference trainers (diffusion_RDUnet.py:117-178,
-    main_diffusion_RDUnet.py:275-336, diffusion_RDUnet_direct.py:266-327); they
-    differ only in the validation sampler and the checkpoint directory.
-
-    accumulation='reference' keeps the reference's update rule:
-    train_step_checkpointed zeroes the gradients at its top (:78), so only the
-    clipped gradient of every ``accumulation_steps``-th batch reaches
-    ``optimizer.step()`` (:126-128).  The other batches' backward, clip and (DDP)
-    all-reduce are skipped -- their gradient is discarded by the reference -- while
-    their timestep draw and, when logged, their forward loss still run, so the
-    parameters are the reference's bit for bit at a third of those batches' cost.
-    accumulation='fixed' accumulates the gradients of ``accumulation_steps``
-    batches and clips + steps once (the rule of UNet/RDUNet_model.py:201-215).
-    ``skip_discarded=False`` runs the discarded backward passes anyway (the
-    reference's literal work; tests compare the two bit for bit).
-    ``loss_weights``: the ``(mse, charbonnier, ssim)`` weights of the train and
-    validation loss, None for the reference's (0, 1, 0).
-
-    ``captured=True`` replays each batch as one hipGraph (train_graph.TrainStepGraphs,
-    one graph per batch shape and kind, kept on the model) instead of issuing it from
-    Python: in the reference mode the ``accumulation_steps``-th batch replays the whole
-    step (update included), a logged other batch the forward + loss, and an unlogged one
-    only draws its t; in the fixed mode the batches replay backward passes that add into
-    a flat accumulator, the ``accumulation_steps``-th with clip and update.  The update
-    is inside the graph, so the optimizer must be a fused one
-    (``make_optimizer(..., fused=True)``); the parameters, optimizer state and logged
-    losses are the eager loop's bit for bit (``skip_discarded`` has no captured form).
-
-    ``ema`` (optim.EMA, no reference counterpart): an exponential moving average of the
-    weights, updated with every optimizer update -- inside a fused optimizer's launch
-    (eager or captured), by ``ema.update()`` behind a torch optimizer's step.
-    ``Loss/validation`` stays the raw weights' loss; ``Loss/validation_ema`` logs the same
-    batch sampled with the averaged weights, and the checkpoints gain ``ema_state_dict``."""
-    if accumulation not in ACCUMULATION_MODES:
-        raise ValueError(f"accumulation must be one of {ACCUMULATION_MODES}, got {accumulation!r}")
-    graphs = None
-    if captured:
-        from . import train_graph
-        graphs = train_graph.trainer_graphs(model, optimizer, distribution_choice, clip_value, loss_weights)
-    ema_update = use_ema(model, optimizer, ema)
-    dev = next(model.parameters()).device
-    for epoch in range(start_epoch, num_epochs):
-        model.train()
-        optimizer.zero_grad()
-        if captured:
-            train_graph.clear_accumulator(model)   # a leftover partial group is discarded
-        n_batches = len(train_loader) if hasattr(train_loader, "__len__") else 0
-        for batch_idx, (noisy_images, clean_images) in enumerate(train_loader):
-            noisy_images, clean_images = noisy_images.to(dev), clean_images.to(dev)
-            step_now = (batch_idx + 1) % accumulation_steps == 0
-            log_now = batch_idx % log_every == 0
-            if captured:
-                if accumulation == 'fixed':
-                    loss_t = graphs(clean_images, noisy_images, kind='accum_step' if step_now else 'accum')
-                elif step_now or log_now:
-                    loss_t = graphs(clean_images, noisy_images, kind='step' if step_now else 'loss')
-                else:
-                    loss_t = forward_step_device(model, clean_images, noisy_images, distribution_choice,
-                                                 need_loss=False)
-            elif accumulation == 'fixed':
-                loss_t = train_step_device(model, clean_images, noisy_images, optimizer, distribution_choice,
-                                           clip_value, zero_grad=False, clip=False, loss_weights=loss_weights)
-                if step_now:
-                    Fn.clip_grad_norm_(model.parameters(), clip_value)
-            elif step_now or not skip_discarded:
-                loss_t = train_step_device(model, clean_images, noisy_images, optimizer, distribution_choice,
-                                           clip_value, loss_weights=loss_weights)
-            else:
-                loss_t = forward_step_device(model, clean_images, noisy_images, distribution_choice,
-                                             need_loss=log_now, loss_weights=loss_weights)
-            if step_now and not captured:
-                if ema_update:
-                    ema.bind()      # (first step: the average starts as the weights before it)
-                optimizer.step()
-                if ema_update:
-                    ema.update()
-                optimizer.zero_grad()
-            if log_now:
-                loss = loss_t.item()
-                print(f"Epoch [{epoch + 1}/{num_epochs}], Batch [{batch_idx + 1}/{n_batches}], Loss: {loss:.4f}")
-                if writer is not None:
-                    writer.add_scalar('Loss/train', loss, epoch * n_batches + batch_idx)
-        model.eval()
-        validation_loss = ema_loss = float("nan")
-        if val_loader is not None:
-            with torch.no_grad():
-                val_noisy_images, val_clean_images = next(iter(val_loader))
-                val_noisy_images, val_clean_images = val_noisy_images.to(dev), val_clean_images.to(dev)
-                denoised_images = sample(model, val_noisy_images)
-                validation_loss = combined_loss(denoised_images, val_clean_images,
-                                                *Fn.loss_weights_or_default(loss_weights)).item()
-                if ema is not None:
-                    with ema.applied():
-                        ema_loss = combined_loss(sample(model, val_noisy_images), val_clean_images,
-                                                 *Fn.loss_weights_or_default(loss_weights)).item()
-        print(f"Epoch [{epoch + 1}/{num_epochs}], Validation Loss: {validation_loss:.4f}")
-        if ema is not None:
-            print(f"Epoch [{epoch + 1}/{num_epochs}], Validation Loss (EMA weights): {ema_loss:.4f}")
-        if writer is not None:
-            writer.add_scalar('Loss/validation', validation_loss, epoch + 1)
-            if ema is not None:
-                writer.add_scalar('Loss/validation_ema', ema_loss, epoch + 1)
-            if hasattr(writer, "flush"):
-                writer.flush()
-        if scheduler is not None:
-            scheduler.step()
-        save_epoch_checkpoint(model, optimizer, scheduler, epoch + 1, os.path.join(
-            output_dir, f"diffusion_RDUNet_model_checkpointed_epoch_{epoch + 1}.pth"), ema=ema)
-
-
-def save_epoch_checkpoint(model, optimizer, scheduler, epoch, checkpoint_path, ema=None):
-    """The per-epoch checkpoint dict of the trainers (:166-174; ``epoch`` counts from 1);
-    with an EMA also ``ema_state_dict`` (optim.EMA.state_dict(); no reference counterpart)."""
-    os.makedirs(os.path.dirname(checkpoint_path) or ".", exist_ok=True)
-    checkpoint = {
-        'epoch': epoch,
-        'model_state_dict': model.state_dict(),
-        'optimizer_state_dict': optimizer.state_dict(),
-        'scheduler_state_dict': scheduler.state_dict() if scheduler is not None else None,
-    }
-    if ema is not None:
-        ema.use_names_of(model)
-        checkpoint['ema_state_dict'] = ema.state_dict()
-    torch.save(checkpoint, checkpoint_path)
-    print(f"Model checkpoint saved at {checkpoint_path}")
-
-
-def restore_ema(ema, checkpoint, model):
-    """The EMA part of a ``load_checkpoint`` (after the weights are loaded): restore it from
-    ``ema_state_dict``; a checkpoint without one restarts the average from the loaded
-    weights at count 0."""
-    if ema is None:
-        return
-    ema.use_names_of(model)
-    if isinstance(checkpoint, dict) and checkpoint.get('ema_state_dict') is not None:
-        ema.load_state_dict(checkpoint['ema_state_dict'])
-    else:
-        ema.reset_to_weights()
-        print("Checkpoint has no EMA: the average restarts from the loaded weights (0 updates)")
-
-
-def ema_weights(checkpoint, checkpoint_path=""):
-    """The averaged weights of a per-epoch checkpoint dict (``ema_state_dict['shadow']``);
-    a clear error when it was trained without an EMA."""
-    state = checkpoint.get('ema_state_dict') if isinstance(checkpoint, dict) else None
-    if state is None:
-        raise KeyError(f"checkpoint {checkpoint_path!r} holds no EMA weights (no 'ema_state_dict': it was trained "
-                       "without --ema_decay, or it is a bare state_dict; the file train() writes as "
-                       "*_final_ema.pth loads with weights='model')")
-    return state['shadow']
-
-
-def load_checkpoint(model, optimizer, scheduler, checkpoint_path, *, ema=None):
-    """diffusion_RDUnet.py:180-193 (weights-only safe load); ``ema``: restored too (restore_ema)."""
-    if (checkpoint_path is not None) and os.path.isfile(checkpoint_path):
-        print(f"Loading checkpoint '{checkpoint_path}'")
-        dev = next(model.parameters()).device
-        checkpoint = torch.load(checkpoint_path, map_location=dev, weights_only=True)
-        model.load_state_dict(checkpoint['model_state_dict'])
-        optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
-        if scheduler is not None and checkpoint.get('scheduler_state_dict') is not None:
-            scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
-        restore_ema(ema, checkpoint, model)
-        start_epoch = checkpoint['epoch']
-        print(f"Loaded checkpoint '{checkpoint_path}' (epoch {start_epoch})")
-        return start_epoch
-    print(f"No checkpoint found at '{checkpoint_path}'")
-    return 0
-
-
-def load_data(args):
-    """diffusion_RDUnet.py:222-228 dispatch on ``args.dataset_choice``;
-    ``args.data_pipeline == 'gpu'``: the device-side loaders of ``synth`` over the same
-    folders (no worker processes)."""
-    if getattr(args, "data_pipeline", "pil") == 'gpu':
-        from . import synth
-        kw = dict(batch_size=args.batch_size, augment=args.augment, dataset_percentage=args.dataset_percentage,
-                  validation_split=args.validation_split, use_rgb=True)
-        if args.dataset_choice == 'DIV2K':
-            return synth.load_data_gpu('dataset/DIV2K_train_HR.nosync', **kw)
-        return synth.load_sidd_data_gpu('dataset/SIDD_dataset.nosync/SIDD_Medium_Srgb', **kw)
-    from .data_loader import load_data as load_div2k_data, load_sidd_data
-    if args.dataset_choice == 'DIV2K':
-        return load_div2k_data('dataset/DIV2K_train_HR.nosync', batch_size=args.batch_size, augment=args.augment,
-                               dataset_percentage=args.dataset_percentage, validation_split=args.validation_split,
-                               use_rgb=True, num_workers=args.num_workers)
-    return load_sidd_data('dataset/SIDD_dataset.nosync/SIDD_Medium_Srgb', batch_size=args.batch_size,
-                          augment=args.augment, dataset_percentage=args.dataset_percentage,
-                          validation_split=args.validation_split, use_rgb=True, num_workers=args.num_workers)
+    main_diffusion_RDUnet.py:275-336, diffusion_RDUnet_direct.py:266-327), which differ only in
+    the validation sampler ``sample`` and the checkpoint directory: ``trainer.train_epochs`` on
+    a ``DiffusionTask`` (see there for ``accumulation``, ``skip_discarded``, ``captured`` and
+    ``ema``).  ``loss_weights``: the ``(mse, charbonnier, ssim)`` weights of the train and
+    validation loss, None for the reference's (0, 1, 0)."""
+    train_epochs(DiffusionTask(model, distribution_choice, loss_weights, sample), train_loader, val_loader, optimizer,
+                 scheduler, writer, os.path.join(output_dir, CHECKPOINT_NAME), num_epochs, start_epoch,
+                 accumulation_steps, clip_value, log_every, accumulation, skip_discarded, captured, ema)
 
 
 def make_optimizer(args, params, fused=False):
@@ -414,38 +260,6 @@ def make_optimizer(args, params, fused=False):
         optimizer = adadelta(params, lr=args.lr)
         scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=3, gamma=0.5)
     return optimizer, scheduler
-
-
-def add_ema_arguments(parser):
-    """``--ema_decay`` / ``--ema_warmup`` (no reference counterpart), on every trainer's parser.
-    Optional additions to the reference's namespaces: a flag that is not given leaves no
-    attribute behind (``argparse.SUPPRESS``) and ``make_ema`` reads them with the defaults
-    0 (no EMA) and False."""
-    parser.add_argument('--ema_decay', type=float, default=argparse.SUPPRESS,
-                        help="keep an exponential moving average of the weights with this decay (default 0: none), "
-                             "validate with it too and save it in the checkpoints")
-    parser.add_argument('--ema_warmup', action='store_true', default=argparse.SUPPRESS,
-                        help="ramp the EMA decay as min(decay, (1 + n) / (10 + n)) over the first updates")
-    return parser
-
-
-def make_ema(args, model):
-    """The optim.EMA the ``--ema_decay`` / ``--ema_warmup`` flags ask for, or None."""
-    decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
-    if decay <= 0.0:
-        return None
-    from .optim import EMA
-    return EMA(model, decay, warmup=bool(getattr(args, "ema_warmup", False)))
-
-
-def save_final_ema(model, ema, path):
-    """The averaged weights as a bare ``state_dict`` of ``model`` (what ``denoise_image
-    --checkpoint`` and ``model.load_state_dict`` take as it is)."""
-    ema.use_names_of(model)
-    state = model.state_dict()
-    state.update(ema.state_dict()['shadow'])
-    torch.save(state, path)
-    print(f"Final EMA weights saved at {path}")
 
 
 def train(args, train_loader=None, val_loader=None):
@@ -483,33 +297,20 @@ def build_parser():
     """diffusion_RDUnet.py:293-309, plus --dtype, --accumulation, the three
     weights of ``combined_loss`` (:60), --step_mode, --data_pipeline and the EMA flags."""
     parser = argparse.ArgumentParser(description="Train a diffusion model with optional optimizer and scheduler choice.")
-    parser.add_argument('--dataset_choice', type=str, default='SIDD', choices=['DIV2K', 'SIDD'])
-    parser.add_argument('--checkpoint_path', type=str, default=None)
-    parser.add_argument('--num_epochs', type=int, default=300)
-    parser.add_argument('--batch_size', type=int, default=8)
-    parser.add_argument('--num_workers', type=int, default=8)
-    parser.add_argument('--validation_split', type=float, default=0.2)
-    parser.add_argument('--augment', action='store_false')
-    parser.add_argument('--dataset_percentage', type=float, default=0.1)
+    add_data_arguments(parser)
     parser.add_argument('--base_filters', type=int, default=32)
     parser.add_argument('--timesteps', type=int, default=20)
     parser.add_argument('--optimizer_choice', type=str, default='adamw', choices=['adam', 'adamw', 'adadelta'])
     parser.add_argument('--scheduler_choice', type=str, default='step', choices=['cosine', 'step'])
-    parser.add_argument('--output_dir', type=str, default='checkpoints')
     parser.add_argument('--lr', type=float, default=1e-4)
     parser.add_argument('--weight_decay', type=float, default=1e-4)
     parser.add_argument('--distribution_choice', type=str, default='uniform', choices=['uniform', 'biased'])
-    parser.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
     parser.add_argument('--accumulation', type=str, default='reference', choices=list(ACCUMULATION_MODES),
                         help="reference: only every 4th batch's gradient is applied (the reference's rule, "
                              "without the discarded backward passes); fixed: accumulate 4 batches")
     parser.add_argument('--mse_weight', type=float, default=0.0)
     parser.add_argument('--charbonnier_weight', type=float, default=1.0)
     parser.add_argument('--ssim_weight', type=float, default=0.0, help="weight of 1 - SSIM (gaussian 11x11)")
-    parser.add_argument('--step_mode', type=str, default='eager', choices=['eager', 'graph'],
-                        help="graph: fused optimizer, every batch replayed as one captured hipGraph")
-    parser.add_argument('--data_pipeline', type=str, default='pil', choices=['pil', 'gpu'],
-                        help="gpu: patches cut and augmented on the device (synth loaders), no worker processes")
     add_ema_arguments(parser)
     return parser
 

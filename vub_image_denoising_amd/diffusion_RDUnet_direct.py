@@ -37,7 +37,7 @@ def train_model_checkpointed(model, train_loader, val_loader, optimizer, schedul
                              start_epoch=0, accumulation_steps=4, clip_value=1.0, *, accumulation='reference',
                              loss_weights=None, captured=False, ema=None):
     """diffusion_RDUnet_direct.py:266-327 (validation with direct_sampling; ``captured``, ``ema``: see
-    run_epochs)."""
+    trainer.train_epochs)."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, CHECKPOINT_DIR, 'uniform', num_epochs,
                start_epoch, accumulation_steps, clip_value, 1, sample=_sample, accumulation=accumulation,
                loss_weights=loss_weights, captured=captured, ema=ema)

@@ -8,8 +8,9 @@ declares inline (:24-352): the network classes, ``DiffusionModel``, the losses,
 * ``train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler,
   writer, num_epochs=10, start_epoch=0, accumulation_steps=4, clip_value=1.0)`` —
   improved_sampling validation, checkpoints under ``checkpoints/`` (:275-336);
-* ``load_checkpoint(model, optimizer, scheduler, checkpoint_path)`` — restores
-  the scheduler unconditionally (:339-352).
+* ``load_checkpoint(model, optimizer, scheduler, checkpoint_path)`` (:339-352) — the
+  one loader of ``trainer``: unlike the reference's it also takes a path of None (no
+  checkpoint: epoch 0) and a scheduler, or a checkpoint's scheduler state, of None.
 
 The script's module-level model / Adam(2e-4) / CosineAnnealingLR(T_max=10)
 (:228-231) stay in the user's script; ``make_training_objects`` builds the same
@@ -17,14 +18,12 @@ four objects for callers that want them.
 """
 from __future__ import annotations
 
-import os
-
-import torch
 import torch.optim as optim
 from torch.optim.lr_scheduler import CosineAnnealingLR
 
 from .diffusion_RDUnet import (DiffusionModel, add_ema_arguments, charbonnier_loss, combined_loss,  # noqa: F401
-                               denormalize, device, make_ema, restore_ema, run_epochs, train_step_device)
+                               denormalize, device, load_checkpoint, make_ema, restore_ema, run_epochs,
+                               train_step_device)
 from .Unet_model import (DenoisingBlock, DownsampleBlock, InputBlock, OutputBlock, RDUNet_T,  # noqa: F401
                          UpsampleBlock, init_weights)
 
@@ -69,25 +68,7 @@ def _sample(model, x):
 def train_model_checkpointed(model, train_loader, val_loader, optimizer, scheduler, writer, num_epochs=10,
                              start_epoch=0, accumulation_steps=4, clip_value=1.0, *, accumulation='reference',
                              loss_weights=None, captured=False, ema=None):
-    """main_diffusion_RDUnet.py:275-336 (``captured``, ``ema``: see run_epochs)."""
+    """main_diffusion_RDUnet.py:275-336 (``captured``, ``ema``: see trainer.train_epochs)."""
     run_epochs(model, train_loader, val_loader, optimizer, scheduler, writer, CHECKPOINT_DIR, 'uniform', num_epochs,
                start_epoch, accumulation_steps, clip_value, 1, sample=_sample, accumulation=accumulation,
                loss_weights=loss_weights, captured=captured, ema=ema)
-
-
-def load_checkpoint(model, optimizer, scheduler, checkpoint_path, *, ema=None):
-    """main_diffusion_RDUnet.py:339-352 (weights-only safe load); ``ema``: restored too
-    (diffusion_RDUnet.restore_ema)."""
-    if os.path.isfile(checkpoint_path):
-        print(f"Loading checkpoint '{checkpoint_path}'")
-        dev = next(model.parameters()).device
-        checkpoint = torch.load(checkpoint_path, map_location=dev, weights_only=True)
-        model.load_state_dict(checkpoint['model_state_dict'])
-        optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
-        scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
-        restore_ema(ema, checkpoint, model)
-        start_epoch = checkpoint['epoch']
-        print(f"Loaded checkpoint '{checkpoint_path}' (epoch {start_epoch})")
-        return start_epoch
-    print(f"No checkpoint found at '{checkpoint_path}'")
-    return 0

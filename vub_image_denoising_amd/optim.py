@@ -12,8 +12,10 @@ resumed run continues bit-identically (diffusion_RDUnet.py:180-193 resume path).
 What ``train_graph.TrainStepGraph`` needs from a fused optimizer is the surface
 of ``FusedFlatOptimizer``: ``graph_buffers()`` (the flat state to snapshot and
 restore around warm-up steps), ``graph_key()`` (the hyperparameters and buffer
-addresses a capture bakes in), ``use_device_step()``, ``set_step()`` and
-``_replayed()``.
+addresses a capture bakes in), ``use_device_step()`` (which also binds),
+``host_counts()`` / ``set_host_counts()`` (the step count and an attached EMA's update
+count, which warm-up steps and the capture advance and must give back),
+``check_ema_not_swapped()`` and ``_replayed()``.
 
 ``EMA`` (no reference counterpart) keeps an exponential moving average of the weights
 in one more flat buffer.  Attached to a fused optimizer (``attach_ema``) it is updated
@@ -115,6 +117,23 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
             else:
                 self._step_dev = torch.full((), self._step, dtype=torch.int64, device=self._fp.device)
 
+    def host_counts(self):
+        """The host counts a step advances: the step count and an attached EMA's update count (else None)."""
+        return self._step, None if self.ema is None else self.ema.num_updates
+
+    def set_host_counts(self, counts, device=True):
+        """Roll the counts back to an earlier ``host_counts()``; ``device`` as in ``set_step``
+        (an EMA's device counter is one of ``graph_buffers()`` and is restored with them)."""
+        self.set_step(counts[0], device)
+        if self.ema is not None:
+            self.ema.num_updates = counts[1]
+
+    def check_ema_not_swapped(self, who):
+        """An update now would train the averaged weights: refuse inside ``EMA.applied()``."""
+        if self.ema is not None and self.ema.swapped:
+            raise RuntimeError(f"{who}: the attached EMA is swapped into the weights (inside EMA.applied()); "
+                               "swap back first")
+
     def reset_state(self):
         """Forget the state and the step count, in place (the flat state buffers
         and device step counter keep their addresses, so a TrainStepGraph captured
@@ -184,9 +203,7 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        if self.ema is not None and self.ema.swapped:
-            raise RuntimeError(f"{type(self).__name__}.step(): the attached EMA is swapped into the weights "
-                               "(inside EMA.applied()); swap back first")
+        self.check_ema_not_swapped(f"{type(self).__name__}.step()")
         fp = self._bind()
         self._step += 1
         self._steps.fill_(self._step)

@@ -30,7 +30,7 @@ The graph owns the parameters' ``.grad`` (views of the flat gradient buffer its
 backward writes); an eager step in between is allowed and does not disturb it.
 
 Besides the full step (``kind='step'``) a graph can capture the other batches the
-trainers issue (diffusion_RDUnet.run_epochs): ``'loss'`` (the t draw, forward and
+trainers issue (trainer.train_epochs): ``'loss'`` (the t draw, forward and
 loss of a batch whose gradient the reference discards, forward_step_device),
 ``'accum'`` (t draw, forward, loss, backward, the gradient added into the model's
 flat accumulator) and ``'accum_step'`` (the same, then clip and update on the
@@ -41,10 +41,10 @@ its own flat buffer and ONE flat ``add_`` folds it in (eager accumulation is 207
 per-tensor adds of the same elements: the same bits).  After an accumulate replay the
 parameters' ``.grad`` are views of the accumulator, as after eager accumulation.
 
-The model may also be a bare ``RDUNet`` (the plain baseline, RDUNet_model.train_model):
-the network is then the model itself and the body is the baseline's batch -- no t draw,
-no interpolation, ``L1(model(noisy), clean)`` -- in the same four kinds.  Such a graph
-has no t buffer (passing ``t`` raises) and no loss weights.
+What a batch is comes from the model's *task* (``trainer``'s module docstring;
+``model.train_task(distribution_choice, loss_weights)`` unless one is passed): a
+DiffusionModel's is the step described above, a bare ``RDUNet``'s (the plain baseline)
+``L1(model(noisy), clean)`` with no t and no loss weights, in the same four kinds.
 """
 from __future__ import annotations
 
@@ -52,24 +52,17 @@ import os
 
 import torch
 
-from . import RDUNet_model as baseline
-from .diffusion_RDUnet import forward_step_device, sample_biased, train_step_device
 from .engine import find_flat
-from .functional import clip_grad_norm_, loss_weights_or_default
+from .functional import clip_grad_norm_
 
 KINDS = ("step", "loss", "accum", "accum_step")
-_FUSED_SURFACE = ("graph_buffers", "graph_key", "use_device_step", "set_step", "_replayed")
+_FUSED_SURFACE = ("graph_buffers", "graph_key", "use_device_step", "host_counts", "set_host_counts",
+                  "check_ema_not_swapped", "_replayed")
 
 
 def is_fused(optimizer) -> bool:
     """The optimizer has what a captured step needs (optim.FusedFlatOptimizer's surface)."""
     return all(hasattr(optimizer, a) for a in _FUSED_SURFACE)
-
-
-def network_of(model):
-    """The fused network a step trains: a DiffusionModel's ``unet``, or the model itself
-    (a bare RDUNet, the baseline)."""
-    return getattr(model, "unet", model)
 
 
 def grad_accumulator(fp):
@@ -85,10 +78,10 @@ def grad_accumulator(fp):
     return acc, fp._accum_views
 
 
-def clear_accumulator(model):
-    """Discard a partial accumulation group (the trainers' ``optimizer.zero_grad()`` at the
-    start of an epoch)."""
-    fp = getattr(network_of(model), "_rdn_flat", None)
+def clear_accumulator(network):
+    """Discard a partial accumulation group of the fused ``network`` (the trainers'
+    ``optimizer.zero_grad()`` at the start of an epoch)."""
+    fp = getattr(network, "_rdn_flat", None)
     if fp is not None and getattr(fp, "_accum", None) is not None:
         fp._accum.zero_()
 
@@ -144,64 +137,53 @@ def _node_count(g):
 
 class TrainStepGraph:
     def __init__(self, model, optimizer, shape, distribution_choice='uniform', clip_value=1.0, t_input=False,
-                 warmup=2, loss_weights=None, kind='step'):
+                 warmup=2, loss_weights=None, kind='step', *, task=None):
         if not is_fused(optimizer):
             raise TypeError("TrainStepGraph needs a fused optimizer (optim.FusedAdam / FusedAdamW / FusedAdadelta)")
         if kind not in KINDS:
             raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
-        self.net = network_of(model)
-        self.baseline = self.net is model     # no t, no interpolation, L1 loss (RDUNet_model.train_step_device)
-        if self.baseline and (t_input or loss_weights is not None):
-            raise ValueError("a bare RDUNet's step has no t input and no loss weights (its loss is L1)")
+        self.task = task = task or model.train_task(distribution_choice, loss_weights)
+        if t_input and not task.takes_t:
+            raise ValueError(f"the step of a {type(model).__name__} has no t input")
+        self.net = task.network
         sync = getattr(getattr(self.net, "_rdn_flat", None), "grad_sync", None)
         if kind != 'step' and sync is not None and sync.world > 1:
             raise NotImplementedError(f"data-parallel capture of kind {kind!r} is not implemented (only 'step')")
         self.kind = kind
         self.model, self.opt = model, optimizer
-        self.dist, self.clip = distribution_choice, clip_value
-        self.loss_weights = loss_weights    # (mse, charbonnier, ssim) of combined_loss; None: (0, 1, 0)
+        self.clip = clip_value
         dev = next(model.parameters()).device
         self.dev = dev
         self.clean = torch.zeros(shape, dtype=torch.float32, device=dev)
         self.noisy = torch.zeros(shape, dtype=torch.float32, device=dev)
-        self.host_t = distribution_choice == 'biased' and not self.baseline
-        self.t = torch.zeros(shape[0], dtype=torch.float32, device=dev) if (t_input or self.host_t) else None
+        self.t = torch.zeros(shape[0], dtype=torch.float32, device=dev) if (t_input or task.host_t) else None
         self.graph = None
         self._build(warmup)
 
     # ------------------------------------------------------------------
     def _hyper(self):
-        """Everything baked into the captured graph: hyperparameters, the loss
-        weights, the compute dtype, and the addresses of the buffers the optimizer
-        updates (a rebound optimizer or a re-flattened model re-captures instead of
-        replaying onto freed memory)."""
-        return (self.opt.graph_key(), float(self.clip), self.net.compute_dtype,
-                'l1' if self.baseline else loss_weights_or_default(self.loss_weights))
+        """Everything baked into the captured graph: hyperparameters, the task's own
+        (the loss and its weights), the compute dtype, and the addresses of the buffers
+        the optimizer updates (a rebound optimizer or a re-flattened model re-captures
+        instead of replaying onto freed memory)."""
+        return self.opt.graph_key(), float(self.clip), self.net.compute_dtype, self.task.graph_key
 
-    def _train_step(self, clip=True):
+    def _backward(self, clip=True):
         """Backward of this batch alone (gradients zeroed first), clipped or not."""
-        if self.baseline:
-            return baseline.train_step_device(self.model, self.noisy, self.clean, self.opt, self.clip,
-                                              zero_grad=True, clip=clip)
-        return train_step_device(self.model, self.clean, self.noisy, self.opt, self.dist, self.clip, t=self.t,
-                                 clip=clip, loss_weights=self.loss_weights)
+        return self.task.train_batch(self.clean, self.noisy, self.opt, self.clip, zero_grad=True, clip=clip, t=self.t)
 
     def _body(self):
         if self.kind == 'loss':
-            if self.baseline:
-                self.model.train()
-                return baseline.forward_loss_device(self.model, self.noisy, self.clean)
-            return forward_step_device(self.model, self.clean, self.noisy, self.dist, t=self.t, need_loss=True,
-                                       loss_weights=self.loss_weights)
+            return self.task.loss_batch(self.clean, self.noisy, need_loss=True, t=self.t)
         if self.kind == 'step':
-            loss = self._train_step()
+            loss = self._backward()
             self.opt.step()
             return loss
         # 'accum' / 'accum_step': this backward's gradient lands in a flat buffer of its
         # own (the parameters' .grad are dropped first), one flat add folds it into the
         # accumulator, and .grad become the accumulator's views, which clip and the
         # update then see as the flat gradient
-        loss = self._train_step(clip=False)
+        loss = self._backward(clip=False)
         params = list(self.model.parameters())
         fp = find_flat(params)
         if fp is None:
@@ -218,29 +200,25 @@ class TrainStepGraph:
 
     def _build(self, warmup):
         rng = torch.cuda.get_rng_state(self.dev)
-        params = list(self.model.parameters())
+        params, opt = list(self.model.parameters()), self.opt
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            if find_flat(params) is None or self.opt._fp is None:
+            if find_flat(params) is None:
                 # gradients as flat views, so the optimizer can bind (no update yet)
-                self._train_step()
-            self.opt.use_device_step()
-            fp, opt = self.opt._fp, self.opt
+                self._backward()
+            opt.use_device_step()    # (binds the optimizer to the flat parameters)
+            fp = find_flat(params)
             state = [fp.flat] + opt.graph_buffers()
             if self.kind in ('accum', 'accum_step'):
                 state.append(grad_accumulator(fp)[0])   # may hold a partial group: kept
             snap = [b.clone() for b in state]
-            step0 = opt._step
-            ema = getattr(opt, "ema", None)
-            ema0 = 0 if ema is None else ema.num_updates
+            counts = opt.host_counts()
             for _ in range(max(1, warmup)):
                 self._body()
             for b, s in zip(state, snap):
                 b.copy_(s)
-            opt.set_step(step0)
-            if ema is not None:
-                ema.num_updates = ema0       # (its device counter is one of the restored buffers)
+            opt.set_host_counts(counts)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize(self.dev)
         _drain_collectives(fp)
@@ -256,9 +234,7 @@ class TrainStepGraph:
         self.graph = g
         self._captured = self._hyper()
         # capture ran nothing: undo its host-side effects (step count, pack keys)
-        opt.set_step(step0, device=False)
-        if ema is not None:
-            ema.num_updates = ema0
+        opt.set_host_counts(counts, device=False)
         fp.generation += 1
         torch.cuda.set_rng_state(rng, self.dev)
 
@@ -266,23 +242,20 @@ class TrainStepGraph:
     def __call__(self, clean_images, noisy_images, t=None):
         """One train step on this batch; returns the loss (a device tensor, valid
         until the next call)."""
-        ema = getattr(self.opt, "ema", None)
-        if ema is not None and ema.swapped:
-            raise RuntimeError("TrainStepGraph: the optimizer's EMA is swapped into the weights (inside "
-                               "EMA.applied()); swap back before training on")
+        self.opt.check_ema_not_swapped("TrainStepGraph")
         if self._hyper() != self._captured:
             self._build(1)
         self.clean.copy_(clean_images)
         self.noisy.copy_(noisy_images)
         if self.t is not None:
             if t is None:
-                if not self.host_t:
+                if not self.task.host_t:
                     raise ValueError("this graph was built with t_input=True: pass t")
-                t = sample_biased(self.clean.size(0), self.model.timesteps)
+                t = self.task.draw_t(self.clean.size(0))
             self.t.copy_(t)
         elif t is not None:
-            raise ValueError("a bare RDUNet's step takes no t" if self.baseline else
-                             "this graph draws t itself (build it with t_input=True to pass t)")
+            raise ValueError("this graph has no t input: its step takes no t, or draws it itself (build it with "
+                             "t_input=True to pass t)")
         self.graph.replay()
         if self.kind in ('step', 'accum_step'):
             self.opt._replayed()
@@ -299,10 +272,10 @@ class TrainStepGraphs:
     stream, so the alternation is the same sequence of steps as eager training."""
 
     def __init__(self, model, optimizer, distribution_choice='uniform', clip_value=1.0, t_input=False, warmup=2,
-                 loss_weights=None):
+                 loss_weights=None, *, task=None):
         self.model, self.opt = model, optimizer
-        self.kw = dict(distribution_choice=distribution_choice, clip_value=clip_value, t_input=t_input,
-                       warmup=warmup, loss_weights=loss_weights)
+        self.kw = dict(clip_value=clip_value, t_input=t_input, warmup=warmup,
+                       task=task or model.train_task(distribution_choice, loss_weights))
         self.graphs = {}
         self.captures = 0
 
@@ -315,21 +288,17 @@ class TrainStepGraphs:
         return g(clean_images, noisy_images, t)
 
 
-def trainer_graphs(model, optimizer, distribution_choice='uniform', clip_value=1.0, loss_weights=None):
-    """The TrainStepGraphs of a trainer (run_epochs(captured=True)), kept on the model:
-    a later call with the same optimizer and settings replays what an earlier one
+def trainer_graphs(model, optimizer, distribution_choice='uniform', clip_value=1.0, loss_weights=None, *, task=None):
+    """The TrainStepGraphs of a trainer (trainer.train_epochs(captured=True)), kept on the
+    model: a later call with the same optimizer and settings replays what an earlier one
     captured."""
     if not is_fused(optimizer):
         raise TypeError("captured training needs a fused optimizer: build it with make_optimizer(..., fused=True) "
                         f"(optim.FusedAdam / FusedAdamW / FusedAdadelta), got {type(optimizer).__name__}")
-    if network_of(model) is model:   # a bare RDUNet: no t distribution, L1 loss
-        if loss_weights is not None:
-            raise ValueError("a bare RDUNet trains on L1: no loss weights")
-        key = ('l1', float(clip_value))
-    else:
-        key = (distribution_choice, float(clip_value), loss_weights_or_default(loss_weights))
+    task = task or model.train_task(distribution_choice, loss_weights)
+    key = (task.graph_key[0], float(clip_value)) + task.graph_key[1:]
     table = model.__dict__.setdefault("_rdn_train_graphs", {})
     g = table.get(key)
     if g is None or g.opt is not optimizer:
-        g = table[key] = TrainStepGraphs(model, optimizer, distribution_choice, clip_value, loss_weights=loss_weights)
+        g = table[key] = TrainStepGraphs(model, optimizer, clip_value=clip_value, task=task)
     return g

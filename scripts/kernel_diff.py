@@ -6,15 +6,19 @@ instruction stream.
     python scripts/kernel_diff.py [OLD [NEW]] conv_gemm.hip conv3_halo.hip
     python scripts/kernel_diff.py HEAD . conv_wgrad.hip wgrad3_halo.hip \\
         --rename 'wgrad_kernelI(\\w+?)Li1EEEv=wgrad_kernelI\\1EEv' --rename 'wgrad3_halo_kernelIf=wgrad3_halo_kernelI'
+    python scripts/kernel_diff.py HEAD . --pool pointwise.hip loss.hip optim.hip
 
 OLD / NEW default to HEAD~1 / HEAD; `.` is the working tree.  Each file is compiled
 device-only to assembly for both revisions (in a temporary directory), each kernel
 is cut at its label ... .Lfunc_end, comments and directives are dropped, the function's
 own symbol and the function number of its .LBB<n>_<m> labels are replaced, and the
 instruction streams are compared per (mangled) name.  --rename 'REGEX=REPL' rewrites
-the OLD names first, for kernels whose template parameter list changed.
+the OLD names first, for kernels whose template parameter list changed.  With --pool the
+kernels of all the files named are pooled per revision and compared by name (a file may
+exist in one revision only): for kernels that moved between files; kernels in anonymous
+namespaces have the same mangled name in every file.
 
-Prints, per file, `identical a/b` (b = kernels present on both sides), then one line
+Prints, per file (per pool), `identical a/b` (b = kernels present on both sides), then one line
 per added, removed or differing kernel.  Exit status 1 if any kernel differs.
 It compares only; it looks at nothing about which instructions appear.
 """
@@ -91,6 +95,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("revs_and_files", nargs="+", metavar="[OLD [NEW]] FILE.hip ...")
     ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL")
+    ap.add_argument("--pool", action="store_true", help="pool the kernels of all files per revision")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     a = ap.parse_intermixed_args()
     files = [os.path.basename(f) for f in a.revs_and_files if f.endswith(".hip")]
@@ -109,10 +114,14 @@ def main():
             checkout(rev, roots[side])
         with cf.ThreadPoolExecutor(a.jobs) as pool:
             asm = {(side, f): pool.submit(compile_asm, roots[side], f) for side in roots for f in files}
-            for f in files:
-                so, sn = asm[("old", f)].result(), asm[("new", f)].result()
-                fo = functions(so) if so else {}
-                fn = functions(sn) if sn else {}
+            def pooled(which, names):
+                out = {}
+                for f in names:
+                    path = asm[(which, f)].result()
+                    out.update(functions(path) if path else {})
+                return out
+            for f, names in ([("pool", files)] if a.pool else [(f, [f]) for f in files]):
+                fo, fn = pooled("old", names), pooled("new", names)
                 for rx, repl in renames:
                     fo = {rx.sub(repl, k): v for k, v in fo.items()}
                 both = sorted(set(fo) & set(fn))

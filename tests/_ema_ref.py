@@ -1,4 +1,4 @@
-"""CPU reference of the weight EMA (csrc/pointwise.hip, ema_weight / ema_elem), in float64.
+"""CPU reference of the weight EMA (csrc/optim.hip, ema_weight / ema_elem), in float64.
 
 One update is ``e <- e + w * (p - e)`` with ``w = float32(1 - d)`` and ``d = decay``, or with
 warm-up ``d = min(decay, (1 + n) / (10 + n))`` for the update after ``n`` earlier ones."""

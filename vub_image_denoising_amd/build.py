@@ -7,7 +7,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["conv_gemm.hip", "conv_pix.hip", "conv3_halo.hip", "conv3_big.hip", "conv3_ws.hip", "conv3_wsd.hip", "conv3_dw.hip", "conv3_dense.hip", "conv3_dense1.hip", "conv_wgrad.hip", "wgrad3_halo.hip", "wgrad3_glds.hip", "pointwise.hip", "synth.hip", "metrics.hip", "tiles.hip", "ssim_loss.hip"]
+SOURCES = ["conv_gemm.hip", "conv_pix.hip", "conv3_halo.hip", "conv3_big.hip", "conv3_ws.hip", "conv3_wsd.hip", "conv3_dw.hip", "conv3_dense.hip", "conv3_dense1.hip", "conv_wgrad.hip", "wgrad3_halo.hip", "wgrad3_glds.hip", "runtime.hip", "prelu_bwd.hip", "pack.hip", "loss.hip", "optim.hip", "synth.hip", "metrics.hip", "tiles.hip", "ssim_loss.hip"]
 # every header a translation unit can include (a touched one rebuilds everything)
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "rdunet_hip.h")]
 OUT = os.path.join(HERE, "librdunet_hip.so")

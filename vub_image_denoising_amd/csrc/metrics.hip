@@ -24,7 +24,7 @@
 // streamed row by row (see the kernel).  Per-block (squared error, sum S) partials in
 // float64; a second launch sums them per image in a fixed order (deterministic).
 // HBM-bound: 8 bytes per pixel read once (+6 columns, +6 rows of halo per tile).
-#include "rdn_common.h"
+#include "rdn_pointwise.h"
 
 #include <math.h>
 
@@ -202,30 +202,13 @@ __global__ __launch_bounds__(NT_MAX, 5) void image_metrics_kernel(const float* _
 __global__ __launch_bounds__(256) void image_metrics_final_kernel(const double* __restrict__ part, int C, int H,
                                                                   int W, int tiles, double range,
                                                                   double* __restrict__ psnr, double* __restrict__ ssim) {
-  __shared__ double red[2][256];
-  const int n = blockIdx.x, t = threadIdx.x;
-  const int slots = C * tiles;
-  double se = 0.0, sc = 0.0;
-  for (int k = t; k < slots; k += 256) {
-    const int64_t slot = (int64_t)n * slots + k;
-    se += part[2 * slot];
-    sc += part[2 * slot + 1];
-  }
-  red[0][t] = se;
-  red[1][t] = sc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) {
-      red[0][t] += red[0][t + o];
-      red[1][t] += red[1][t + o];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
+  const int n = blockIdx.x, slots = C * tiles;
+  double tot[2];   // squared error, sum of S
+  if (final_sums(part + 2 * (int64_t)n * slots, slots, tot)) {
     const double interior = (double)(H - 2 * R) * (double)(W - 2 * R);
-    const double mse = red[0][0] / ((double)C * H * W);
+    const double mse = tot[0] / ((double)C * H * W);
     if (psnr) psnr[n] = 10.0 * log10(range * range / mse);   // mse == 0 -> inf, as skimage
-    if (ssim) ssim[n] = red[1][0] / interior / C;
+    if (ssim) ssim[n] = tot[1] / interior / C;
   }
 }
 

@@ -25,7 +25,7 @@
 //
 // Both are HBM/LDS-bound stencil passes: 4-byte accesses coalesced along x (rows of an
 // arbitrary W are not 16-byte aligned), 64-bit plane offsets.
-#include "rdn_common.h"
+#include "rdn_pointwise.h"
 
 #include <math.h>
 
@@ -48,12 +48,6 @@ static SsimTaps make_taps() {
   }
   for (int i = 0; i < kWin; ++i) t.g[i] /= s;
   return t;
-}
-
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // rows r0 .. r0+3 of column c of a row-filtered field [kHalo][kTile], filtered along y
@@ -132,26 +126,9 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
       }
     }
   }
-  sum = wave_sum64(sum);
-  if ((tid & 63) == 0) red[tid >> 6] = sum;
-  __syncthreads();
+  block_wave_sums(sum, red);
   if (tid == 0)
     part[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the partials in block order, strided over one block's threads, summed in float64
-__global__ __launch_bounds__(256) void ssim_final_kernel(const float* __restrict__ part, int nb, double count,
-                                                         float* __restrict__ out) {
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 256) s += part[i];
-  __shared__ double sh[256];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)(sh[0] / count);
 }
 
 __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -250,7 +227,7 @@ extern "C" int rdn_ssim_fwd(const float* x, const float* y, int32_t n, int32_t c
   const dim3 grid = tile_grid(n, c, oh, ow);
   const int nb = (int)(grid.x * grid.y * grid.z);
   ssim_fwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, y, h, w, make_taps(), c1, c2, coef, count, ws);
-  ssim_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(ws, nb, (double)count, out);
+  mean_final_kernel<1><<<1, 256, 0, (hipStream_t)stream>>>(ws, nb, (double)count, out);
   return rdn_check_launch("rdn_ssim_fwd");
 }
 

@@ -274,7 +274,7 @@ class FusedAdadelta(FusedFlatOptimizer):
 def ema_decay_at(decay, warmup, n):
     """The decay of the update after ``n`` earlier ones: ``decay``, or with warm-up
     ``min(decay, (1 + n) / (10 + n))`` (0.1 for the first update, rising to the cap).
-    In double, the expression the kernels evaluate (csrc/pointwise.hip, ema_weight)."""
+    In double, the expression the kernels evaluate (csrc/optim.hip, ema_weight)."""
     return min(float(decay), (1.0 + n) / (10.0 + n)) if warmup else float(decay)
 
 

@@ -480,6 +480,45 @@ int rdn_tile_gather(const float* img, int32_t n, int32_t c, int32_t h, int32_t w
 int rdn_tile_blend(const float* tiles /* [n*ny*nx, c, th, tw] */, int32_t n, int32_t c, int32_t h, int32_t w,
                    int32_t tile, int32_t overlap, float* out /* [n, c, h, w] */, void* stream);
 
+/* Geometric self-ensemble over the same tile grid: each tile is denoised under the first
+   n_ens of the 8 flips and transposes of the square and the results, mapped back, are
+   averaged before the blend.
+   Transform d in 0..7: bit 0 flips x, bit 1 flips y, bit 2 transposes, applied after the
+   flips (torch: u.flip(-1) if d&1, then u.flip(-2) if d&2, then u.transpose(-1,-2) if d&4).
+   For a tile u of th x tw:  T_d(u)[y', x'] = u[sy, sx]  with
+     (y, x) = (x', y') if d&4 else (y', x');  sy = th-1-y if d&2 else y;  sx = tw-1-x if d&1 else x.
+   T_d(u) is tw x th when d&4; the inverse transposes first and then flips.
+   Ensemble n_ens in {1, 2, 4, 8} uses d = 0..n_ens-1 (2: identity and x-flip, 4: the four
+   flips, 8: all of D4), per tile of the grid (the grid pads and clamps at the bottom /
+   right, so it is not symmetric).  Tile g becomes
+     e_g = (((v_0 + v_1) + v_2) + ... + v_{n_ens-1}) * (1/n_ens),  v_d = T_d^-1(sampler(T_d(tile g))),
+   an fp32 sum in ascending d, not contracted, times an exact power of two;
+   rdn_tile_blend then blends e_g unchanged.
+   A pass is the transforms d0 .. d0+nd-1, which share one tile shape: square tiles take one
+   pass (0, n_ens); otherwise (0, min(n_ens, 4)) and, for n_ens == 8, (4, 4) on tw x th
+   tiles.  Work item w = g*nd + (d - d0), 0 <= w < n_tiles*nd (tile-major: the transforms of
+   a tile are adjacent); a batch is `count` consecutive items from `first`, and the sum
+   order is ascending d however the batches cut it.
+   Both entries return RDN_E_ARG before any launch, the message naming the argument, unless
+   nd >= 1, d0 >= 0, d0 + nd <= 8, the pass does not straddle d = 4 on non-square tiles,
+   first >= 0, count >= 1 and no pointer is null; rdn_tile_gather_d4 also checks the grid as
+   rdn_tile_gather does, rdn_tile_accum_d4 that n_ens is 1, 2, 4 or 8, d0 + nd <= n_ens,
+   n_tiles >= 1, 1 <= c <= 8 and th, tw are multiples of 8.
+
+   tiles[j] = T_d(tile g) of img for work item first+j, j < count: [count, c, th, tw], or
+   [count, c, tw, th] for a pass with d0 >= 4.  Reflect padding applies in source
+   coordinates; an item past the last repeats the last item. */
+int rdn_tile_gather_d4(const float* img, int32_t n, int32_t c, int32_t h, int32_t w, int32_t tile, int32_t overlap,
+                       int32_t d0, int32_t nd, int64_t first, int32_t count, float* tiles, void* stream);
+/* src holds the sampler's output for work items first .. first+count-1 (in the shape the
+   gather produced; items past the end are ignored), acc is [n_tiles, c, th, tw].  For each
+   tile the range touches, one thread owns each element and walks the tile's d values in the
+   range in ascending order: d == 0 stores without reading acc (acc may be uninitialised),
+   any other d adds to the stored partial sum, d == n_ens-1 also multiplies by 1/n_ens.  No
+   two threads of a launch write one element; no atomics. */
+int rdn_tile_accum_d4(const float* src, float* acc, int64_t n_tiles, int32_t c, int32_t th, int32_t tw, int32_t d0,
+                      int32_t nd, int32_t n_ens, int64_t first, int32_t count, void* stream);
+
 const char* rdn_version(void);
 const char* rdn_last_error(void);
 

@@ -153,6 +153,8 @@ SIGNATURES = {
     "rdn_tile_grid": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     "rdn_tile_gather": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _vp]),
     "rdn_tile_blend": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "rdn_tile_gather_d4": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _vp]),
+    "rdn_tile_accum_d4": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp]),
     "rdn_version": (C.c_char_p, []),
     "rdn_last_error": (C.c_char_p, []),
 }

@@ -10,7 +10,8 @@ checkpoint is either form the trainers write -- the per-epoch dict with
 ``model_state_dict`` or the final bare ``state_dict`` -- read with ``weights_only=True``.
 ``--weights ema`` takes the averaged weights of a per-epoch checkpoint trained with
 ``--ema_decay`` (its ``ema_state_dict``); the ``*_final_ema.pth`` file is a bare
-``state_dict`` and loads as it is.
+``state_dict`` and loads as it is.  ``--ensemble {2,4,8}`` averages every tile over its
+flips (and transposes): the geometric self-ensemble of ``sampling.denoise_tiled``.
 """
 from __future__ import annotations
 
@@ -34,6 +35,9 @@ def build_parser():
     p.add_argument('--timesteps', type=int, default=20)
     p.add_argument('--weights', type=str, default='model', choices=['model', 'ema'],
                    help="ema: the averaged weights of a checkpoint trained with --ema_decay")
+    p.add_argument('--ensemble', type=int, default=1, choices=[1, 2, 4, 8],
+                   help="geometric self-ensemble: average over 2 (x-flip), 4 (flips) or 8 (flips and transposes) "
+                        "transforms of every tile; 1: off")
     return p
 
 
@@ -76,7 +80,7 @@ def main(argv=None):
     model = load_model(args.checkpoint, args.base_filters, args.timesteps, args.dtype, weights=args.weights)
     with Image.open(args.input) as img:
         noisy = image_to_tensor(img).cuda()
-    out = model.denoise_image(noisy, tile=args.tile, overlap=args.overlap, sampler=args.sampler)
+    out = model.denoise_image(noisy, tile=args.tile, overlap=args.overlap, sampler=args.sampler, ensemble=args.ensemble)
     tensor_to_image(out).save(args.output)
     print(f"{args.input}: {noisy.size(3)}x{noisy.size(2)} -> {args.output}")
     return 0

@@ -92,13 +92,17 @@ def main(noisy_mat_file="evaluate_SIDD/ValidationNoisyBlocksSrgb.mat",
          gt_mat_file="evaluate_SIDD/ValidationGtBlocksSrgb.mat",
          checkpoint_path="checkpoints/diffusion_RDUNet_model_checkpointed_epoch_40.pth",
          evaluation_percentage=0.1, batch_size=1, base_filters=32, timesteps=20, out_csv="benchmark_results.csv",
-         weights="model"):
+         weights="model", ensemble=1):
     """evaluate_SIDD.py:102-148 (the checkpoint is read with weights_only=True).
     ``weights='ema'`` scores the averaged weights of a checkpoint trained with an EMA
-    (its ``ema_state_dict['shadow']``; an error if it has none)."""
+    (its ``ema_state_dict['shadow']``; an error if it has none).  ``ensemble`` in {2, 4, 8}
+    scores the geometric self-ensemble (``DiffusionModel.denoise_image``): a 256 x 256
+    block is one tile, so its transforms go through the sampler as one batch."""
     from .diffusion_RDUnet import DiffusionModel, ema_weights
     if weights not in ("model", "ema"):
         raise ValueError(f"weights must be 'model' or 'ema', got {weights!r}")
+    if ensemble not in (1, 2, 4, 8):
+        raise ValueError(f"ensemble must be 1, 2, 4 or 8, got {ensemble!r}")
     from .Unet_model import RDUNet_T
     dataset = SIDDMatDataset(noisy_mat_file, gt_mat_file)
     indices = np.random.choice(len(dataset), int(len(dataset) * evaluation_percentage), replace=False)
@@ -109,7 +113,8 @@ def main(noisy_mat_file="evaluate_SIDD/ValidationNoisyBlocksSrgb.mat",
         raise FileNotFoundError(f"checkpoint not found: {checkpoint_path}")
     ckpt = torch.load(checkpoint_path, map_location=device, weights_only=True)
     model.load_state_dict(ema_weights(ckpt, checkpoint_path) if weights == "ema" else ckpt["model_state_dict"])
-    avg_psnr, avg_ssim, avg_time, samples = evaluate_model(model, dataloader, device)
+    sampler = (lambda x: model.denoise_image(x, ensemble=ensemble)) if ensemble > 1 else None
+    avg_psnr, avg_ssim, avg_time, samples = evaluate_model(model, dataloader, device, sampler=sampler)
     print(f"Average PSNR: {avg_psnr:.2f}")
     print(f"Average SSIM: {avg_ssim:.4f}")
     print(f"Average Inference Time: {avg_time:.2f} ms")

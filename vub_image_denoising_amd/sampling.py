@@ -21,7 +21,9 @@ MI355X-first changes, each bit-exact:
 
 ``denoise_tiled`` (no reference counterpart) runs either sampler over whole images of
 any size: overlapping tiles of one fixed shape through one captured SamplerGraph,
-gathered and blended by ``rdn_tile_gather`` / ``rdn_tile_blend``.
+gathered and blended by ``rdn_tile_gather`` / ``rdn_tile_blend``.  With
+``ensemble`` > 1 each tile is denoised under 2, 4 or 8 flips / transposes sharing sampler
+batches, transformed and averaged by ``rdn_tile_gather_d4`` / ``rdn_tile_accum_d4``.
 """
 from __future__ import annotations
 
@@ -174,6 +176,50 @@ def tile_blend(tiles, out, tile, overlap):
     return out
 
 
+ENSEMBLES = (1, 2, 4, 8)
+
+
+def ensemble_passes(ensemble, th, tw):
+    """The passes ``(d0, nd)`` of a geometric self-ensemble on th x tw tiles: transforms
+    ``d0 .. d0+nd-1`` share one tile shape (``include/rdunet_hip.h``, rdn_tile_gather_d4)."""
+    if th == tw:
+        return [(0, ensemble)]
+    return [(0, min(ensemble, 4))] + ([(4, 4)] if ensemble == 8 else [])
+
+
+def tile_gather_d4(img, tile, overlap, d0, nd, first, count, out=None):
+    """Work items ``first .. first+count-1`` of the pass ``(d0, nd)`` over the tiles of
+    ``img`` [B,C,H,W]: item ``g*nd + (d - d0)`` is tile ``g`` under transform ``d``, as
+    [count,C,th,tw] ([count,C,tw,th] for ``d0 >= 4``); an item past the last repeats the
+    last (``rdn_tile_gather_d4``)."""
+    H.require_device(img)
+    B, C, Hh, Ww = img.shape
+    th, tw, _, _ = plan_tiles(Hh, Ww, tile, overlap)
+    if out is None:
+        shape = (count, C, tw, th) if d0 >= 4 else (count, C, th, tw)
+        out = torch.empty(shape, dtype=torch.float32, device=img.device)
+    H.check(H.lib().rdn_tile_gather_d4(img.data_ptr(), B, C, Hh, Ww, tile, overlap, d0, nd, first, count, out.data_ptr(),
+                                       H.stream_ptr()), "tile_gather_d4")
+    return out
+
+
+def tile_accum_d4(src, acc, d0, nd, n_ens, first, count=None):
+    """Map the sampler outputs ``src`` of work items ``first .. first+count-1`` of the pass
+    ``(d0, nd)`` back and add them into the running ensemble mean ``acc`` [n_tiles,C,th,tw]
+    in ascending ``d`` (``rdn_tile_accum_d4``).  ``count`` defaults to ``src.size(0)``."""
+    H.require_device(src, acc)
+    n_tiles, C, th, tw = acc.shape
+    count = src.size(0) if count is None else count
+    want = (C, tw, th) if d0 >= 4 else (C, th, tw)
+    if src.dim() != 4 or tuple(src.shape[1:]) != want or src.size(0) < count:
+        raise RuntimeError(f"tile_accum_d4: expected src [>= {count}, {want}], got {tuple(src.shape)}")
+    if src.dtype != torch.float32 or acc.dtype != torch.float32 or not (src.is_contiguous() and acc.is_contiguous()):
+        raise RuntimeError("tile_accum_d4: src and acc must be contiguous fp32")
+    H.check(H.lib().rdn_tile_accum_d4(src.data_ptr(), acc.data_ptr(), n_tiles, C, th, tw, d0, nd, n_ens, first, count,
+                                      H.stream_ptr()), "tile_accum_d4")
+    return acc
+
+
 def _tile_sampler(model, shape, sampler, graph):
     """The sampler for tile batches of ``shape``: eager, or the model's cached SamplerGraph."""
     direct = sampler == "direct"
@@ -190,7 +236,8 @@ def _tile_sampler(model, shape, sampler, graph):
     return hit[1]
 
 
-def denoise_tiled(model, noisy, *, tile=512, overlap=32, sampler="improved", tile_batch=None, graph=True):
+def denoise_tiled(model, noisy, *, tile=512, overlap=32, sampler="improved", tile_batch=None, graph=True,
+                  ensemble=1):
     """Denoise whole images of any size H, W >= 8: ``noisy`` [B,C,H,W] (device, fp32) is cut
     into overlapping tiles of one shape (``plan_tiles``), ``tile_batch`` tiles at a time go
     through the sampler (``improved_sampling`` or ``direct_sampling``), and the results are
@@ -198,9 +245,20 @@ def denoise_tiled(model, noisy, *, tile=512, overlap=32, sampler="improved", til
     one captured SamplerGraph, kept on the model, serve every image size; memory is bounded
     by the tile batch.  A region covered by one tile is that tile's sampler output bit for
     bit.  Tiling is not the untiled network: the receptive field is far wider than the
-    overlap, so results differ from an untiled run wherever there is more than one tile."""
+    overlap, so results differ from an untiled run wherever there is more than one tile.
+
+    ``ensemble`` in {1, 2, 4, 8}: the geometric self-ensemble.  Every tile goes through the
+    sampler under the first ``ensemble`` flips / transposes of the square (2: identity and
+    x-flip, 4: the four flips, 8: all of D4) and the results, mapped back, are averaged in
+    fp32 in a fixed order before the blend (``rdn_tile_gather_d4`` / ``rdn_tile_accum_d4``,
+    DESIGN.md 3.2).  ``tile_batch`` then counts work items (tile, transform), the transforms
+    of a tile being adjacent, and the result does not depend on it.  Non-square tiles at
+    ``ensemble=8`` run a second pass on transposed tiles: one more engine and one more
+    captured graph.  ``ensemble=1`` is the plain path, launch for launch."""
     if sampler not in ("improved", "direct"):
         raise ValueError(f"sampler must be 'improved' or 'direct', got {sampler!r}")
+    if ensemble not in ENSEMBLES:
+        raise ValueError(f"ensemble must be one of {ENSEMBLES}, got {ensemble!r}")
     if not isinstance(noisy, torch.Tensor) or noisy.dim() != 4:
         raise RuntimeError("denoise_tiled: expected a [B,C,H,W] tensor")
     H.require_device(noisy, next(model.parameters()))
@@ -208,12 +266,27 @@ def denoise_tiled(model, noisy, *, tile=512, overlap=32, sampler="improved", til
     B, C, Hh, Ww = x.shape
     th, tw, ys, xs = plan_tiles(Hh, Ww, tile, overlap)
     n_tiles = B * len(ys) * len(xs)
+    passes = ensemble_passes(ensemble, th, tw)
     if tile_batch is None:
         # the batched improved sampler runs 2B images: stay below run_unet's chunking threshold
         k = 2 if sampler == "improved" else 1
-        tile_batch = max(1, min(n_tiles, E.FWD_CHUNK_PIXELS // (k * th * tw)))
+        tile_batch = max(1, min(n_tiles * max(nd for _, nd in passes), E.FWD_CHUNK_PIXELS // (k * th * tw)))
     if tile_batch < 1:
         raise ValueError(f"tile_batch must be >= 1, got {tile_batch}")
+    if ensemble > 1:
+        with torch.no_grad():
+            tout = torch.empty((n_tiles, C, th, tw), dtype=torch.float32, device=x.device)
+            out = torch.empty_like(x)
+            for d0, nd in passes:
+                shape = (tile_batch, C, tw, th) if d0 >= 4 else (tile_batch, C, th, tw)
+                run = _tile_sampler(model, shape, sampler, graph)
+                tin = torch.empty(shape, dtype=torch.float32, device=x.device)
+                for first in range(0, n_tiles * nd, tile_batch):
+                    tile_gather_d4(x, tile, overlap, d0, nd, first, tile_batch, out=tin)
+                    # the surplus of the last batch is ignored; the running mean lives in tout
+                    tile_accum_d4(run(tin).contiguous(), tout, d0, nd, ensemble, first, tile_batch)
+            tile_blend(tout, out, tile, overlap)
+        return out
     with torch.no_grad():
         run = _tile_sampler(model, (tile_batch, C, th, tw), sampler, graph)
         tin = torch.empty((tile_batch, C, th, tw), dtype=torch.float32, device=x.device)
